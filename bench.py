@@ -13,9 +13,13 @@ observations, rewards, terminated/truncated flags and sampled actions to its own
 shard with no data-path collective; the final obs/reward/terminated/truncated tensors of every --gather-every steps are
 all-gathered over RCCL asynchronously, overlapping the next launches (north_star; gym/vector/utils/numpy_utils.py:49-50).
 
-Timing.  The timed region is --steps vector steps, bracketed by barrier + synchronize.  When that is shorter than --min-timed-ms
-the region is REPEATED back to back inside the same bracket, `config.repeats` times, and every figure is per step of that longer
-run.  The launch shape does not depend on --steps: the rollout always advances in --chunk-step launches.
+Timing.  The timed region is exactly --steps vector steps, bracketed by barrier + synchronize; `ms_per_step` is its length over
+--steps.  Only when asked (--min-timed-ms M or --repeats R) is the region REPEATED back to back inside the same bracket,
+`config.repeats` times, and every figure is then per step of that longer run.  The rollout advances in launches of --chunk steps
+(the last one shorter when --steps is not a multiple of --chunk).
+
+--dump-outputs DIR writes what the last timed step returned (obs, reward, terminated, truncated, actions of rank 0's envs) as
+DIR/<name>.npy in float32 / float64; the inputs are a pure function of the arguments, so two builds compare output for output.
 
 Output.  stdout carries ONE JSON line of less than 4 KB (tests/test_gpu_bench_line.py): the contract fields, `config`
 (workload, launch shape, work_check, launch_info, per-rank reports), `roofline` (HIP events on the engine's stream; algorithmic
@@ -140,8 +144,9 @@ def parse_args():
     ap.add_argument("--mode", default="fused", choices=["fused", "graph", "eager"],
                     help="fused: one launch per chunk, env state in registers; graph/eager: one launch per step")
     ap.add_argument("--no-graph", action="store_true", help="alias of --mode eager")
-    ap.add_argument("--min-timed-ms", type=float, default=60.0,
-                    help="the timed region is repeated back to back until it is nominally at least this long (see docstring)")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
+                    help="repeat the timed region back to back until it is nominally at least this long (see docstring); 0 (default): "
+                         "exactly --steps timed steps")
     ap.add_argument("--repeats", type=int, default=0, help="force the number of repeats of the timed region (0 = from --min-timed-ms)")
     ap.add_argument("--spinup-ms", type=float, default=150.0,
                     help="nominal length of the untimed device spin-up before the W warmup steps (DVFS: the GPU needs tens of ms of "
@@ -178,6 +183,9 @@ def parse_args():
                     help="where the full record of the secondary measurements goes (the stdout line carries one pair per group); '' disables")
     ap.add_argument("--headline-file", default=os.path.join(ROOT, "gpurun_out", "bench_headline.json"),
                     help="long-form copy of the headline record (prose, per-rank placement reports); '' disables")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's obs / reward / terminated / truncated / actions as DIR/<name>.npy "
+                         "(dumps/<build> in the repository is ignored by git)")
     ap.add_argument("--init-timeout", type=float, default=180.0, help="seconds the process group / first collective may take")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds a self-launched job may take in total")
     return ap.parse_args()

@@ -333,6 +333,8 @@ def run(args, bench_file, cpu_baseline=None):
                           "checksum": work_checksum(term[:, :c], trunc[:, :c], act[:, :c]) if eng.NA > 0 else None,
                           "autoresets_per_env_step": ended / float(k_last * local_envs),
                           "seed": 0, "action_seed": 1}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, traj, timed_steps, args.chunk, eng.stream)
 
     # The gather by itself, blocking, after the timed region (rank 0's wall time of `gather_reps` back-to-back gathers between fences)
     # beside what the link model predicts for it: the first real 8-GPU run can be read in one glance.  And the older cadence — one
@@ -494,6 +496,27 @@ def run(args, bench_file, cpu_baseline=None):
         dist.barrier()
         dist.destroy_process_group()
 
+
+
+DUMP_NAMES = ("obs", "reward", "terminated", "truncated", "actions")
+
+
+def dump_outputs(out_dir, traj, timed_steps, chunk, stream):
+    """--dump-outputs: what the last vector step of the timed region returned to its caller (this rank's shard of obs, reward,
+    terminated, truncated, actions), one DIR/<name>.npy each, float32 (obs, flags) or float64 (reward, actions).  The inputs are a pure
+    function of the arguments (reset(seed=0) after the time-based warm phase), so two builds can be compared array for array.
+    CartPole-v1 at 2^20 envs: 40 MB in all."""
+    import numpy as np
+    import torch
+
+    k = (timed_steps % chunk or chunk) - 1          # the last step's slot of the last chunk-step launch
+    os.makedirs(out_dir, exist_ok=True)
+    with torch.cuda.stream(stream):
+        for name in DUMP_NAMES:
+            x = traj[name][k]
+            dt = torch.float32 if x.dtype in (torch.float32, torch.uint8, torch.bool) else torch.float64
+            np.save(os.path.join(out_dir, name + ".npy"), x.to(dt).cpu().numpy())
+    stream.synchronize()
 
 
 def _write_json(path, obj):

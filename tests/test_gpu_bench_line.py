@@ -17,11 +17,12 @@ sys.path.insert(0, ROOT)
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5`, the driver's command (plus a short CPU sample and side files in a temporary
-    directory): (the stdout line parsed, the raw stdout, the full variant records from the side file, stderr)."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5`, the driver's command, with the 0.1-ms region repeated to 60 ms in one bracket
+    (--min-timed-ms 60), a short CPU sample and side files in a temporary directory: (the stdout line parsed, the raw stdout, the full
+    variant records from the side file, stderr)."""
     d = tmp_path_factory.mktemp("bench")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-sample-steps", "4",
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--min-timed-ms", "60", "--cpu-sample-steps", "4",
                         "--variants-file", str(d / "variants.json"), "--headline-file", str(d / "headline.json")], cwd=ROOT,
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -149,3 +150,67 @@ def test_line_carries_what_the_review_asked_for(run):
     pl = v["policy_loop_4096_envs"]                          # the launch-bound regime: the loop recorded once in a caller's hipGraph
     assert pl["recorded_in_a_hipgraph"]["us_per_step"] < pl["one_call_per_step"]["us_per_step"] and pl["speedup"] > 1.3
     assert min(pl["episodes_ended"]) > 0
+
+
+@pytest.fixture(scope="module")
+def dumped(tmp_path_factory):
+    """The same short command twice with --dump-outputs: [(the stdout line parsed, {name: array})] per run."""
+    from benchmarks.headline import DUMP_NAMES
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for i in range(2):
+        d = tmp_path_factory.mktemp(f"dump{i}")
+        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-variants",
+                            "--variants-file", "", "--headline-file", "", "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True,
+                           timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-3000:]
+        runs.append((json.loads(p.stdout), {n: np.load(d / f"{n}.npy") for n in DUMP_NAMES}))
+    return runs
+
+
+def test_steps_set_the_timed_steps_and_the_dump_holds_the_last_one(dumped):
+    """`--steps 20`: exactly 20 timed steps, ms_per_step over them; the dump is the last step's five arrays, float32 / float64, under
+    64 MB, bit-equal from run to run, and the oracle twin with the same seeds reproduces it."""
+    from oracle.oracle import OracleVecEnv
+
+    (line, out), (line2, out2) = dumped
+    cfg = line["config"]
+    assert (line["steps"], cfg["repeats"], cfg["timed_steps"]) == (20, 1, 20) and line["ms_per_step"] > 0
+    assert line["ms_per_step"] == pytest.approx(cfg["timed_region_ms"] / 20, rel=1e-6)
+    n = 1 << 20
+    assert out["obs"].shape == (n, 4) and all(out[k].shape == (n,) for k in ("reward", "terminated", "truncated", "actions"))
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    for k in out:
+        assert np.array_equal(out[k], out2[k]), k
+    wc = cfg["work_check"]
+    c, t_last = wc["envs"], wc["first_step_index"] + wc["steps"] - 1
+    o = OracleVecEnv(0, c, 500, seed=wc["seed"], action_seed=wc["action_seed"])
+    o.reset(seed=wc["seed"])
+    o.rollout(t_last)
+    a = o.sample_actions()
+    ob, rw, te, tr, _, _ = o.step(a)
+    assert np.array_equal(out["actions"][:c], a) and np.array_equal(out["reward"][:c], rw)
+    assert np.array_equal(out["terminated"][:c], te) and np.array_equal(out["truncated"][:c], tr)
+    np.testing.assert_allclose(out["obs"][:c], ob, rtol=1e-4, atol=1e-6)
+
+
+def test_the_drivers_exact_command():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` and nothing else (variants and CPU baseline on, side files where they go by
+    default): ONE line under 4 KB with the contract fields, exactly 20 timed steps, ms_per_step per step of them."""
+    import bench
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=900, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    raw = p.stdout
+    assert raw.endswith("\n") and len(raw.strip().splitlines()) == 1 and len(raw.encode()) < bench.LINE_LIMIT, len(raw)
+    line = json.loads(raw)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config", "roofline", "cpu_baseline", "variants"):
+        assert k in line, k
+    cfg = line["config"]
+    assert (line["steps"], line["warmup"], cfg["repeats"], cfg["timed_steps"]) == (20, 5, 1, 20)
+    assert line["ms_per_step"] == pytest.approx(cfg["timed_region_ms"] / 20, rel=1e-6)
+    assert line["value"] == pytest.approx((1 << 20) / (line["ms_per_step"] * 1e-3), rel=1e-6)

@@ -31,7 +31,8 @@ def _torchrun(script_args, env=None, timeout=240):
 
 def test_bench_two_ranks_strong_scaling_is_the_default():
     """BASELINE.json's metric: 2^20 logical envs in total, partitioned over the ranks (gather included in the timed region)."""
-    lines = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "512", "--warmup", "256", "--no-cpu-baseline"])
+    lines = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "512", "--warmup", "256", "--min-timed-ms", "60",
+                       "--no-cpu-baseline"])
     assert len(lines) == 1          # rank 0 prints the one line
     out = lines[0]
     assert out["n_gpus"] == 2 and out["steps"] == 512 and out["scaling"] == "strong"
@@ -46,10 +47,10 @@ def test_bench_two_ranks_strong_scaling_is_the_default():
 
 
 def test_bench_two_ranks_weak_scaling_and_the_drivers_short_run():
-    """--scaling weak keeps 2^20 envs per GPU; `--steps 20 --warmup 5` (what the driver passes) must repeat the 0.1-ms region
-    inside one bracket instead of timing a single launch, with the byte accounting of the launches that really ran."""
+    """--scaling weak keeps 2^20 envs per GPU; `--steps 20 --warmup 5` (what the driver passes) with --min-timed-ms 60 must repeat the
+    0.1-ms region inside one bracket instead of timing a single launch, with the byte accounting of the launches that really ran."""
     lines = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--scaling", "weak", "--steps", "20", "--warmup", "5",
-                       "--no-cpu-baseline"])
+                       "--min-timed-ms", "60", "--no-cpu-baseline"])
     out = lines[0]
     assert out["scaling"] == "weak" and out["config"]["num_envs_per_gpu"] == 1 << 20 and out["steps"] == 20
     cfg, roof = out["config"], out["roofline"]
@@ -73,7 +74,8 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did():
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run sets them) and the ONE line says how many ranks the
     communicator spanned and what every rank measured."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "20", "--warmup", "5"], cwd=ROOT,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "20", "--warmup", "5",
+                        "--min-timed-ms", "60"], cwd=ROOT,
                        capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     # stdout is the ONE line and nothing else: what gloo / RCCL print when a communicator comes up ("[Gloo] Rank 0 is connected ...",

@@ -69,7 +69,7 @@ def test_the_gather_inside_the_timed_region_at_world_size_1(comm):
     """--comm mxv: libmxv.so opens RCCL itself, builds a one-rank communicator and issues the grouped ncclAllGather calls of every chunk
     on its side stream, overlapping the next launch — the code an 8-GPU run executes, minus the links."""
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--comm", comm, "--force-gather", "--gather-every", "256", "--steps", "1024", "--warmup", "256",
-                        "--no-cpu-baseline", "--no-variants", "--placement", "off", "--warm-max-s", "0.4"], cwd=ROOT, capture_output=True,
+                        "--min-timed-ms", "60", "--no-cpu-baseline", "--no-variants", "--placement", "off", "--warm-max-s", "0.4"], cwd=ROOT, capture_output=True,
                        text=True, timeout=300, env=_env())
     out = _one_line(p)
     cfg = out["config"]

@@ -602,43 +602,41 @@ def test_vector_utils_without_the_reference():
 
 @pytest.mark.parametrize("gid", ["CartPole-v1", "Pendulum-v1", "Acrobot-v1", "MountainCar-v0", "MountainCarContinuous-v0"])
 def test_call_state_has_the_references_container_types(gid, monkeypatch):
-    """VectorEnv.call("state") against the LIVE reference (skipped where /root/reference is absent): after reset() and after a step the
-    reference's sub-envs hold their state in different containers (ndarray of the generator's dtype vs tuple / float32 array); the
-    adapter reproduces container, dtype and shape — and `_elapsed_steps`, `_max_episode_steps`, `render_mode` — value for value."""
+    """VectorEnv.call("state") against the reference's answers (tests/golden/live_call_state.json, make_golden_live.py: a SyncVectorEnv of 3
+    envs after reset(seed=1) and after a step of the recorded actions): the reference's sub-envs hold their state in different
+    containers (ndarray of the generator's dtype vs tuple / float32 array); the adapter reproduces container, dtype and shape — and
+    `_elapsed_steps`, `_max_episode_steps`, `render_mode` — value for value."""
+    import json
     import os
-    if not os.path.isdir("/root/reference/gym"):
-        pytest.skip("the reference tree is not here (GPU box)")
-    import importlib.util
-    spec_ = importlib.util.spec_from_file_location("make_golden_live2", os.path.join(os.path.dirname(__file__), "golden", "make_golden.py"))
-    mg = importlib.util.module_from_spec(spec_)
-    spec_.loader.exec_module(mg)
+
     from oracle_engine import FakeHandle
 
     import gym_amd
     from gym_amd import _native
 
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_call_state.json")) as f:
+        phases = json.load(f)[gid]
     monkeypatch.setattr(_native, "Handle", FakeHandle)
-    ref = mg.gym.vector.make(gid, num_envs=3, asynchronous=False)
     env = gym_amd.make(gid, num_envs=3)
-    ref.reset(seed=1), env.reset(seed=1)
+    env.reset(seed=1)
 
-    def same_kind(a, b):
-        assert type(a) is type(b) or (isinstance(a, np.ndarray) and isinstance(b, np.ndarray)), (type(a), type(b))
-        if isinstance(a, np.ndarray):
-            assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype)
+    def same_kind(a, want):
+        if want["type"] == "ndarray":
+            assert isinstance(a, np.ndarray), (type(a), want)
+            assert str(a.dtype) == want["dtype"] and list(a.shape) == want["shape"], (a.dtype, a.shape, want)
         else:
-            assert len(a) == len(b) and all(isinstance(x, float) for x in a)
+            assert type(a).__name__ == want["type"] and len(a) == want["len"], (type(a), want)
+            assert want["all_float"] and all(isinstance(x, float) for x in a)
 
-    for phase in ("after reset", "after a step"):
-        ra, ea = ref.call("state"), env.call("state")
+    for ph in phases:        # after reset, after a step
+        ea = env.call("state")
         assert isinstance(ea, tuple) and len(ea) == 3
-        for a, b in zip(ea, ra):
-            same_kind(a, b)
-        assert env.call("_elapsed_steps") == ref.call("_elapsed_steps") and env.call("_max_episode_steps") == ref.call("_max_episode_steps")
-        assert env.call("render_mode") == ref.call("render_mode")
-        act = ref.action_space.sample()
-        ref.step(act), env.step(act)
-    ref.close(), env.close()
+        for a, want in zip(ea, ph["state"]):
+            same_kind(a, want)
+        assert list(env.call("_elapsed_steps")) == ph["_elapsed_steps"] and list(env.call("_max_episode_steps")) == ph["_max_episode_steps"]
+        assert list(env.call("render_mode")) == ph["render_mode"]
+        env.step(np.asarray(ph["action"], dtype=ph["action_dtype"]))
+    env.close()
 
 
 def test_partials_are_attached_and_detached_by_call_shape():
@@ -767,15 +765,12 @@ def test_vector_make_recognises_the_sub_env_wrappers_it_can_map():
         with pytest.raises(NotImplementedError) as e:
             _sub_env_wrappers(bad)
         assert needle in str(e.value), (bad, str(e.value))
-    try:                                                                                   # the reference's own classes, where it is importable
-        import sys
-        sys.path.insert(0, "/root/reference")
-        for name, val in (("bool8", np.bool_), ("float_", np.float64)):
-            if not hasattr(np, name):
-                setattr(np, name, val)
-        from gym.wrappers import RecordEpisodeStatistics as RefStats, TimeLimit as RefLimit
-    except Exception:  # noqa: BLE001
-        return
+    # classes with the reference's own names and home modules (tests/golden/live_reference_facts.json, make_golden_live.py)
+    import json
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_reference_facts.json")) as f:
+        homes = json.load(f)["wrappers"]
+    RefLimit, RefStats = (type(n, (), {"__module__": homes[n]}) for n in ("TimeLimit", "RecordEpisodeStatistics"))
     assert _sub_env_wrappers([functools.partial(RefLimit, max_episode_steps=30), RefStats]) == (30, [("episode_statistics", {})])
 
 
