@@ -32,17 +32,11 @@ namespace {
 constexpr int kBjBlock = 256;
 constexpr uint32_t kStreamDraw = 5u;
 constexpr unsigned kBjXcds = 8;   // MI355X: consecutive workgroup ids go round the 8 XCDs
-#ifndef MXV_BJ_TILEMAP
-#define MXV_BJ_TILEMAP 1          // 1: XCD x steps (and stores) the x-th contiguous eighth of the tables; 0: tile = workgroup id (A/B hook)
-#endif
+// XCD x steps (and stores) the x-th contiguous eighth of the tables (tile = workgroup id: 0.5 us slower, profiles/r5/r5c_blackjack_tilemap_placement_ab.txt)
 __device__ __forceinline__ unsigned bj_tile(unsigned bid, unsigned ntiles) {
-#if MXV_BJ_TILEMAP
     const unsigned x = bid % kBjXcds, idx = bid / kBjXcds;
     const unsigned base = ntiles / kBjXcds, rem = ntiles % kBjXcds;
     return x * base + (x < rem ? x : rem) + idx;
-#else
-    return bid;
-#endif
 }
 
 struct Hand {
@@ -138,17 +132,15 @@ template <> struct BjOut<2> { using I = int32_t; using R = float; };    // the c
 //   OUT     : output dtypes.
 // Both arms of `if action:` (:123-146) are evaluated for every lane and selected — under random or learned policies every wave holds
 // hitters and stickers, so a branch would run both anyway, plus its bookkeeping.
-#ifndef MXV_BJ_WAVES
-#define MXV_BJ_WAVES 8   // 8: 64 VGPRs and <= 96 SGPRs = two full rounds of the 16 waves per SIMD a 2^20-table launch needs (no spills); 0: the allocator's choice (63 VGPRs but 7 waves: SGPRs) (A/B hook)
-#endif
+// 8 waves per SIMD: 64 VGPRs and <= 96 SGPRs = two full rounds of the 16 waves per SIMD a 2^20-table launch needs (no spills); the
+// allocator's own choice, 63 VGPRs but 7 waves (SGPRs), runs as fast: profiles/r5/r5d_blackjack_waves_scalar_base_ab.txt.
+constexpr int kBjWaves = 8;
 // STATS (round 6): the episode-statistics accumulators (mxv_bj_episode_stats) are an instantiation of their own — the kernel sits exactly
 // at the 64-VGPR budget of 8 waves per SIMD, and as a run-time branch the three extra live values put 32 bytes of every launch's lanes
 // into scratch, statistics or not.  The STATS = true twins may take 7 waves.
 template <bool INJ, bool SAMPLED, int OUT, bool STATS = false>
 __global__ void __launch_bounds__(kBjBlock)
-#if MXV_BJ_WAVES > 0
-    __attribute__((amdgpu_waves_per_eu(STATS ? 4 : MXV_BJ_WAVES, MXV_BJ_WAVES)))
-#endif
+    __attribute__((amdgpu_waves_per_eu(STATS ? 4 : kBjWaves, kBjWaves)))
     bj_kernel(BjArgs a) {
     using I = typename BjOut<OUT>::I;
     using R = typename BjOut<OUT>::R;

@@ -18,10 +18,6 @@
 #define MXV_XCOLD __device__ __noinline__ inline
 #include "mxv_exact.hpp"
 
-#ifndef MXV_CARTPOLE_RCP
-#define MXV_CARTPOLE_RCP 1  // tuning hook: 0 = the compiler's `/` for CartPole's one runtime division
-#endif
-
 namespace mxv {
 
 struct EnvParams {
@@ -58,21 +54,12 @@ constexpr double kPi = 3.141592653589793;
 // use inside the loop, where from the second iteration on they wait for the acknowledgement of the stores of the previous
 // (and the current) step — the whole HBM write latency, once per wave and step.  With the loads settled at entry the loop
 // body carries no vmcnt wait at all and a wave keeps several steps of output stores in flight.
-#ifndef MXV_SETTLE_LOADS
-#define MXV_SETTLE_LOADS 1  // tuning hook: 0 = leave the waits where the compiler puts them
-#endif
-__device__ __forceinline__ void settle_entry_loads() {
-#if MXV_SETTLE_LOADS
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
-}
+__device__ __forceinline__ void settle_entry_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 // The same for a load INSIDE the loop on a conditional path (per-env seeds of a reset draw): using the value in the branch
 // that loaded it keeps the compiler's vmcnt wait inside that branch instead of at the join every wave passes through.
 template <typename T>
 __device__ __forceinline__ T landed(T v) {
-#if MXV_SETTLE_LOADS
     asm volatile("" : "+v"(v));
-#endif
     return v;
 }
 
@@ -112,18 +99,11 @@ __device__ __forceinline__ uint32_t xor3_vgpr(uint32_t x, uint32_t y, uint32_t z
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(d) : "v"(x), "v"(y), "v"(z));
     return d;
 }
-// x ^ (y & mask) in one instruction (mask: a wave-uniform constant, taken from an SGPR)
-#ifndef MXV_BITOP3_SIGNS
-#define MXV_BITOP3_SIGNS 1   // A/B hook (which env kinds use the form: MXV_BITOP3_ENVS below)
-#endif
+// x ^ (y & mask) in one instruction (mask: a wave-uniform constant, taken from an SGPR; which env kinds use it: fma3_for below)
 __device__ __forceinline__ uint32_t xor_masked(uint32_t x, uint32_t y, uint32_t mask) {
-#if MXV_BITOP3_SIGNS
     uint32_t d;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x78" : "=v"(d) : "v"(x), "v"(y), "s"(mask));
     return d;
-#else
-    return x ^ (y & mask);
-#endif
 }
 __device__ __forceinline__ U4 philox4x32_10_vkey(U4 c, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -259,19 +239,12 @@ __device__ __forceinline__ double div_with_rcp(double x, double d, double r) {
 // state injection) append the hardware's own special-case pass, v_div_fixup_f64 — what the compiler's `/` ends with: the quotient goes
 // through unchanged for ordinary operands, NaN / Inf / 0 operands get IEEE's answers — one instruction instead of the ten of a full division
 // (round 4 first used `/` here: step(actions) 18.5 -> 20.1 us per 2^20-env step).
-#ifndef MXV_GUARDED_DIV_FIXUP
-#define MXV_GUARDED_DIV_FIXUP 1   // A/B hook
-#endif
 template <int DEF, bool FINITE = true>
 __device__ __forceinline__ double div_par(double x, double c) {
     if constexpr (DEF == PM_DEFAULT && FINITE)
         return div_by_const(x, c, 1.0 / c);  // c is a literal on this path: 1.0 / c folds at compile time
     else if constexpr (DEF == PM_DEFAULT)
-#if MXV_GUARDED_DIV_FIXUP
         return __builtin_amdgcn_div_fixup(div_by_const(x, c, 1.0 / c), c, x);
-#else
-        return div_by_const(x, c, 1.0 / c);
-#endif
     else
         return x / c;
 }
@@ -289,48 +262,18 @@ __device__ __forceinline__ double div_par(double x, double c) {
 // instructions per env-step).  The three-address form reads the coefficient where it is.  Same operation, same bits.
 // It pays where the coefficients stay in registers across the loop (Pendulum, MountainCarContinuous: -7 % / -9 % instructions in the
 // K-step loop); the kernels at their 128-VGPR budget (CartPole and MountainCar at two envs per lane, Acrobot) re-materialise or spill
-// instead, so the form is chosen per env kind: bit `env id` of MXV_FMA3_ENVS (A/B hook; profiles/r3/r3p_fma3_ab.jsonl).
-#ifndef MXV_FMA3_ENVS
-#define MXV_FMA3_ENVS ((1 << MXV_PENDULUM) | (1 << MXV_MOUNTAINCAR_CONT))
-#endif
+// instead, so the form is chosen per env kind: bit 0 of fma3_for<ENV>() (profiles/r3/r3p_fma3_ab.jsonl).
 // (The same with the coefficients in SGPR pairs — 20 VGPRs freed for 20 SGPRs — was tried for the register-bound kernels: Acrobot -1 % of its
 // loop's VALU instructions, every other kind more: dropped.)
 // CartPole with ONE env per lane (shards of up to 2^17 envs: the per-GPU share of an 8-GPU strong-scaling job, latency-bound, 87 VGPRs)
 // gains 5 % (0.818 -> 0.778 us per step); at two envs per lane (113 VGPRs) it is the compiler's form that wins.
-#ifndef MXV_FMA3_CARTPOLE_E1
-#define MXV_FMA3_CARTPOLE_E1 1
-#endif
-// ... and bit 1 of the same per-kind flag word: the quadrant signs of sincos_medium as v_bitop3_b32 (xor_masked) — Acrobot and Pendulum
-// lose 2 instructions per sincos, MountainCar (cosine only, two envs per lane) gains 15 in its loop: chosen per env kind as well.
-#ifndef MXV_BITOP3_ENVS
-#define MXV_BITOP3_ENVS ((1 << MXV_ACROBOT) | (1 << MXV_PENDULUM))
-#endif
-// ... bit 2 (round 6): the twelve polynomial coefficients of sincos_kernel read from a table in constant memory by SCALAR loads inside every
-// call and used as the FMAs' scalar operand (v_fma_f64 v, v, v, s[..]).  A kernel at its VGPR cap re-materialises the literals next to
-// every Horner step — 20 of sincos_medium's 52 VALU instructions are v_mov_b32 of coefficient halves, 8 sincos per Acrobot step —
-// and keeping them in SGPRs ACROSS the loop spills (round 3's attempt: -1 %).  Loaded where they are used (s_load_dwordx8 x 3 through a
-// pointer the optimiser cannot see through, so the loads are not hoisted) they cost the scalar unit three instructions and the
-// vector unit none: sincos_medium alone goes from 52 to 36 VALU instructions.  MEASURED in the kernel that matters (round 6, Acrobot,
-// 2^19 envs): 583.4 -> 579.2 VALU instructions per env-step and the same 10.5 us — inside the K-step loop the compiler already keeps
-// the coefficients in ~24 VGPRs across the steps, so the 20 moves were never executed per call; the form only frees those registers
-// (128 -> 126 VGPRs, 4 -> 0 spilled).  An A/B hook, off (profiles/r6/r6h_acrobot_valu.md).
-#ifndef MXV_SCOEF_ENVS
-#define MXV_SCOEF_ENVS 0
-#endif
+// Bit 1: the quadrant signs of sincos_medium as v_bitop3_b32 (xor_masked) — Acrobot and Pendulum lose 2 instructions per sincos,
+// MountainCar (cosine only, two envs per lane) gains 15 in its loop: chosen per env kind as well.
+// (Coefficients as scalar operands loaded from constant memory inside each call: Acrobot 583.4 -> 579.2 VALU instructions per env-step,
+// the same 10.5 us: dropped, profiles/r6/r6h_acrobot_valu.md.)
 template <int ENV>
 constexpr int fma3_for() {
-    return (((MXV_FMA3_ENVS >> ENV) & 1) ? 1 : 0) | (((MXV_BITOP3_ENVS >> ENV) & 1) ? 2 : 0) | (((MXV_SCOEF_ENVS >> ENV) & 1) ? 4 : 0);
-}
-__constant__ const double kSinCosCoef[12] = {
-    1.58969099521155010221e-10, -2.50507602534068634195e-08, 2.75573137070700676789e-06, -1.98412698298579493134e-04,
-    8.33333333332248946124e-03, -1.66666666666666324348e-01,                                                        // S6 .. S1
-    -1.13596475577881948265e-11, 2.08757232129817482790e-09, -2.75573143513906633035e-07, 2.48015872894767294178e-05,
-    -1.38888888888741095749e-03, 4.16666666666666019037e-02};                                                       // C6 .. C1
-typedef const double __attribute__((address_space(4))) cdouble_t;
-__device__ __forceinline__ double fma_scoef(double a, double b, double k_sgpr) {
-    double r;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(k_sgpr));
-    return r;
+    return ((ENV == MXV_PENDULUM || ENV == MXV_MOUNTAINCAR_CONT) ? 1 : 0) | ((ENV == MXV_ACROBOT || ENV == MXV_PENDULUM) ? 2 : 0);
 }
 
 template <int F3>
@@ -344,30 +287,9 @@ __device__ __forceinline__ double fma_coef(double a, double b, double k) {
     }
 }
 
-#ifndef MXV_FDLIBM_COS
-#define MXV_FDLIBM_COS 0
-#endif
 template <int F3 = 0>
 __device__ __forceinline__ void sincos_kernel(double x, double *sn, double *cs) {
     const double z = x * x;
-    if constexpr ((F3 & 4) != 0) {      // the same FMAs in the same order with ten of the twelve coefficients as scalar operands (MXV_SCOEF_ENVS;
-        cdouble_t *t = (cdouble_t *)kSinCosCoef;   // an instruction reads ONE scalar operand: the leading coefficient of each polynomial stays a literal)
-        asm volatile("" : "+s"(t));
-        double r = fma_scoef(z, 1.58969099521155010221e-10, t[1]);
-        r = fma_scoef(z, r, t[2]);
-        r = fma_scoef(z, r, t[3]);
-        r = fma_scoef(z, r, t[4]);
-        r = fma_scoef(z, r, t[5]);
-        *sn = __fma_rn(x * z, r, x);
-        double c = fma_scoef(z, -1.13596475577881948265e-11, t[7]);
-        c = fma_scoef(z, c, t[8]);
-        c = fma_scoef(z, c, t[9]);
-        c = fma_scoef(z, c, t[10]);
-        c = fma_scoef(z, c, t[11]);
-        c = __fma_rn(z, c, -0.5);
-        *cs = __fma_rn(z, c, 1.0);
-        return;
-    }
     // sin: x + x*z*(S1 + z*(S2 + z*(S3 + z*(S4 + z*(S5 + z*S6)))))
     double r = fma_coef<F3>(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
     r = fma_coef<F3>(z, r, 2.75573137070700676789e-06);
@@ -380,20 +302,14 @@ __device__ __forceinline__ void sincos_kernel(double x, double *sn, double *cs) 
     // two FMAs here (3e7 arguments against 80-bit cosl; 3.6 % vs 4.2 % of the values are not the correctly rounded one).  Five
     // instructions per evaluation (40 of Acrobot's 622 per env-step) for 0.13 ulp of a function whose medium-range version is bounded by
     // its argument reduction anyway: sincos_medium's maxima, 1.466 / 1.498 ulp, are the same with either form (tools/fast_sincos_check.c
-    // -DPLAIN).  MXV_FDLIBM_COS = 1 restores the compensated sum (A/B hook).
+    // -DPLAIN; timing: profiles/r4/r4g_cosine_tail_ab.txt).
     double c = fma_coef<F3>(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
     c = fma_coef<F3>(z, c, -2.75573143513906633035e-07);
     c = fma_coef<F3>(z, c, 2.48015872894767294178e-05);
     c = fma_coef<F3>(z, c, -1.38888888888741095749e-03);
     c = fma_coef<F3>(z, c, 4.16666666666666019037e-02);
-#if MXV_FDLIBM_COS
-    const double hz = 0.5 * z;
-    const double t = 1.0 - hz;
-    *cs = t + __fma_rn(z, z * c, (1.0 - t) - hz);
-#else
     c = __fma_rn(z, c, -0.5);
     *cs = __fma_rn(z, c, 1.0);
-#endif
 }
 
 // General-range sin/cos.  ocml's sincos costs ~80 VALU instructions per call on gfx950 (a 3-term Cody-Waite reduction kept in
@@ -407,9 +323,6 @@ __device__ __forceinline__ void sincos_kernel(double x, double *sn, double *cs) 
 // tools/fast_sincos_check.c), ~35 instructions.  |x| >= 2^19 (k * P1 no longer exact; never produced by these dynamics) goes to
 // ocml.  As everywhere in this file, what happens inside a libm-like helper is the library's business: the reference's own
 // sin/cos are glibc's resp. NumPy's SIMD loops, which differ from each other in the last bit too.
-#ifndef MXV_FAST_TRIG
-#define MXV_FAST_TRIG 1  // A/B hook: 0 = ocml's sincos / cos everywhere
-#endif
 template <int F3 = 0>
 __device__ __forceinline__ void sincos_medium(double x, double *sn, double *cs) {
     const double k = rint(x * 6.36619772367581382433e-01);        // 2/pi
@@ -437,22 +350,16 @@ __device__ __forceinline__ void sincos_medium(double x, double *sn, double *cs) 
 // bounds break that knowledge for one launch, which then takes the guarded instantiation (see launch_step_env, SAFE).
 template <bool GUARD = true, int F3 = 0>
 __device__ __forceinline__ void mx_sincos(double x, double *sn, double *cs) {
-#if MXV_FAST_TRIG
     if (!GUARD || fabs(x) < 524288.0)
         sincos_medium<F3>(x, sn, cs);
     else
-#endif
         sincos(x, sn, cs);
 }
 template <bool GUARD = true, int F3 = 0>
 __device__ __forceinline__ double mx_cos(double x) {
-#if MXV_FAST_TRIG
     double s, c;
     mx_sincos<GUARD, F3>(x, &s, &c);
     return c;
-#else
-    return cos(x);
-#endif
 }
 template <bool GUARD = true, int F3 = 0>
 __device__ __forceinline__ double mx_sin(double x) {
@@ -477,52 +384,29 @@ __device__ __forceinline__ void sincos_small_or_general(double x, double *sn, do
 // by a NaN pass-through: float64 = one v_cmp_u_f64 + one v_cndmask_b32 per dword (both: a NaN whose payload sits in the low dword only
 // — 0x7FF00000:xxxxxxxx, which a caller can craft — would turn into an infinity on a bound's zero low dword otherwise);
 // float32 = nothing extra, gfx950 has the IEEE-754-2019 NaN-propagating v_maximum3_f32 / v_minimum3_f32.
-#ifndef MXV_MINMAX_CLAMPS
-#define MXV_MINMAX_CLAMPS 1   // A/B hook: 0 = compare + select
-#endif
 // np.clip(x, lo, hi) = minimum(maximum(x, lo), hi): the lower bound first (the order only shows when a caller sets lo > hi); NaN passes through
 __device__ __forceinline__ double nan_through(double x, double r) {
     const bool nan = x != x;
     return __hiloint2double(nan ? __double2hiint(x) : __double2hiint(r), nan ? __double2loint(x) : __double2loint(r));
 }
 __device__ __forceinline__ double clamp_range(double x, double lo, double hi) {
-#if MXV_MINMAX_CLAMPS
     return nan_through(x, __builtin_fmin(__builtin_fmax(x, lo), hi));
-#else
-    x = (x < lo) ? lo : x;
-    return (x > hi) ? hi : x;
-#endif
 }
 __device__ __forceinline__ float clamp_range(float x, float lo, float hi) {
-#if MXV_MINMAX_CLAMPS
     float r;
     asm("v_maximum3_f32 %0, %1, %2, %2" : "=v"(r) : "v"(x), "v"(lo));
     asm("v_minimum3_f32 %0, %1, %2, %2" : "=v"(r) : "v"(r), "v"(hi));
     return r;
-#else
-    x = (x < lo) ? lo : x;
-    return (x > hi) ? hi : x;
-#endif
 }
 // `if x > hi: x = hi` then `if x < lo: x = lo` (continuous_mountain_car.py:149-157): the upper bound first
 __device__ __forceinline__ double clamp_range_hi_first(double x, double lo, double hi) {
-#if MXV_MINMAX_CLAMPS
     return nan_through(x, __builtin_fmax(__builtin_fmin(x, hi), lo));
-#else
-    x = (x > hi) ? hi : x;
-    return (x < lo) ? lo : x;
-#endif
 }
 __device__ __forceinline__ float clamp_range_hi_first(float x, float lo, float hi) {
-#if MXV_MINMAX_CLAMPS
     float r;
     asm("v_minimum3_f32 %0, %1, %2, %2" : "=v"(r) : "v"(x), "v"(hi));
     asm("v_maximum3_f32 %0, %1, %2, %2" : "=v"(r) : "v"(r), "v"(lo));
     return r;
-#else
-    x = (x > hi) ? hi : x;
-    return (x < lo) ? lo : x;
-#endif
 }
 
 // C fmod(a, b) for a compile-time b > 0 and |a| < 2^20 * b in ~8 instructions.  fmod is exact by definition, so any
@@ -568,14 +452,14 @@ struct Env<MXV_CARTPOLE> {
         const double force = (ai == 1) ? force_mag : -force_mag;  // :135
         double sintheta, costheta;
         if constexpr (DEF == PM_DEFAULT && !SAFE)
-            sincos_kernel<((fma3_for<MXV_CARTPOLE>() & 1) || (EPL == 1 && MXV_FMA3_CARTPOLE_E1)) ? 1 : 0>(theta, &sintheta, &costheta);
+            sincos_kernel<((fma3_for<MXV_CARTPOLE>() & 1) || EPL == 1) ? 1 : 0>(theta, &sintheta, &costheta);
         else
             sincos_small_or_general(theta, &sintheta, &costheta);  // :136-137
         const double temp = div_par<DEF, !SAFE>(force + polemass_length * (theta_dot * theta_dot) * sintheta, total_mass);  // :141-143
         const double ta_num = gravity * sintheta - costheta * temp;
         const double ta_den = length * (4.0 / 3.0 - div_par<DEF, !SAFE>(masspole * (costheta * costheta), total_mass));  // :144-146
         double thetaacc;
-        if constexpr (DEF == PM_DEFAULT && !SAFE && MXV_CARTPOLE_RCP)  // ta_den in [0.62, 0.67], ta_num normal and never -0: the scale / fix-up
+        if constexpr (DEF == PM_DEFAULT && !SAFE)  // ta_den in [0.62, 0.67], ta_num normal and never -0: the scale / fix-up
             thetaacc = div_with_rcp(ta_num, ta_den, refined_rcp(ta_den));  // steps of `/` are identities (same bits, 3 slots fewer)
         else
             thetaacc = ta_num / ta_den;
@@ -626,7 +510,7 @@ struct Env<MXV_CARTPOLE> {
 // default keeps u * u and x * x — correctly rounded, within 1 ulp of whatever libm the reference runs on, inside north_star's bar by
 // five orders of magnitude — and README's Parity table carries the footnote with these numbers.
 #ifndef MXV_PENDULUM_GLIBC_POWF
-#define MXV_PENDULUM_GLIBC_POWF 0   // 1: restate glibc 2.35's powf(u, 2.0f) (tools/build_variants.sh "...:-DMXV_PENDULUM_GLIBC_POWF=1")
+#define MXV_PENDULUM_GLIBC_POWF 0   // 1: restate glibc 2.35's powf(u, 2.0f) (tools/build_variants.sh "name:-DMXV_PENDULUM_GLIBC_POWF=1")
 #endif
 static __device__ const uint64_t kExp2fTab[32] = {
     0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
@@ -705,11 +589,7 @@ __device__ __forceinline__ double np_remainder(double a, double b) {  // numpy f
 // The same value for a literal b > 0 when the caller knows |a| < 2^20 * b (the fused rollout on a time-limited Pendulum: |theta| < 90),
 // as straight-line selects: no range guard with ocml's fmod behind it, no exec-mask blocks around single additions.  Every step is exact
 // (see fmod_const), so the bits are those of np_remainder by construction.
-#ifndef MXV_REMAINDER_SELECTS
-#define MXV_REMAINDER_SELECTS 1   // A/B hook
-#endif
 __device__ __forceinline__ double np_remainder_bounded(double a, double b) {
-#if MXV_REMAINDER_SELECTS
     const double aa = fabs(a);
     const double q = trunc(aa * (1.0 / b));
     double r = __fma_rn(-q, b, aa);              // exact: the true remainder or off by one period
@@ -719,9 +599,6 @@ __device__ __forceinline__ double np_remainder_bounded(double a, double b) {
     const double lifted = mod + b;               // Python / NumPy `%`: the sign of the divisor
     mod = (mod < 0.0) ? lifted : mod;
     return (mod == 0.0) ? 0.0 : mod;             // copysign(0.0, b) for a zero remainder
-#else
-    return np_remainder(a, b);
-#endif
 }
 
 template <>
@@ -785,26 +662,11 @@ struct Env<MXV_PENDULUM> {
 // and the sin/cos of the post-step angles (the observation) ARE the stage-1 values of the next step, so a fused rollout carries
 // them in registers: 8 sincos per step instead of 6 sincos + 9 cos.
 // What the identities leave out is the ROUNDING OF THE REFERENCE'S ARGUMENTS: it takes the cosine of fl(fl(t1 + t2) - fl(pi/2)), which
-// is off the exact t1 + t2 - pi/2 by up to ~5e-16, i.e. a few ulps of the cosine.  Rounds 2-3 carried those roundings explicitly
-// (three TwoSum residual chains per stage: cos(fl(x - p)) = sin x + (delta - e) cos x, ...; MXV_ACROBOT_CARRY_ARG_ROUNDING = 1): 90 of the
-// kernel's 732 VALU instructions per env-step for agreement to ~2 ulps instead of ~5 per stage cosine — against bars of 1e-12 on the
-// fp64 state and 2 float32 ulps on the observations (golden P1 states: 99 % of post-step state components within 59 fp64 ulps of the
-// reference instead of 16, the worst the same 2.6e-12 relative; tools/acrobot_threshold_ab.c).  Round 4: the mask no longer depends
-// on those ulps (the exact band below decides near the threshold), so the hot path takes the identities as they are.
-#ifndef MXV_ACROBOT_CARRY_ARG_ROUNDING
-#define MXV_ACROBOT_CARRY_ARG_ROUNDING 0   // A/B hook
-#endif
-__device__ __forceinline__ double two_sum_residual(double a, double b, double sum) {  // a + b == sum + residual exactly
-    const double bb = sum - a;
-    return (a - (sum - bb)) + (b - bb);
-}
-constexpr double kHalfPiTail = 6.123233995736766036e-17;  // pi/2 - fl(pi/2)
-#ifndef MXV_ACROBOT_EXACT_BAND
-#define MXV_ACROBOT_EXACT_BAND 1   // A/B hook: 0 = the hot path's mask everywhere (rounds 1-3)
-#endif
-#ifndef MXV_ACROBOT_DIRECT_COS
-#define MXV_ACROBOT_DIRECT_COS 0   // measurement only (tools/acrobot_threshold_ab.py): every cosine evaluated directly, no angle addition
-#endif
+// is off the exact t1 + t2 - pi/2 by up to ~5e-16, i.e. a few ulps of the cosine — against bars of 1e-12 on the fp64 state and 2 float32
+// ulps on the observations (golden P1 states: 99 % of post-step state components within 59 fp64 ulps of the reference, 16 with the
+// roundings carried, the worst the same 2.6e-12 relative).  The mask does not depend on those ulps (the exact band below decides near the
+// threshold), so the hot path takes the identities as they are.  (Carrying the roundings as TwoSum residual chains: 90 more of 732 VALU
+// instructions per env-step, 10.4 -> 12.0 us: profiles/r4/r4b_acrobot_trim.json.)
 
 template <>
 struct Env<MXV_ACROBOT> {
@@ -822,25 +684,10 @@ struct Env<MXV_ACROBOT> {
         const double lc1 = P.get(5, 0.5), lc2 = P.get(6, 0.5), I1 = P.get(7, 1.0), I2 = P.get(7, 1.0);
         const bool nips = P.get(11, 0.0) != 0.0;
         const double g = 9.8;  // :245
-        [[maybe_unused]] const double theta1 = sa[0], theta2 = sa[1];   // (the angles themselves: only the A/B forms below read them)
         const double dtheta1 = sa[2], dtheta2 = sa[3];
         const double s1 = sc[0], c1 = sc[1], s2 = sc[2], c2 = sc[3];
-        [[maybe_unused]] const double halfpi = kPi / 2.0;
         // cos(theta1 + theta2 - pi / 2.0) :259 and cos(theta1 - pi / 2) :264 from the stage's four values (see the trig budget above)
-        const double S12 = __fma_rn(s1, c2, c1 * s2);
-#if MXV_ACROBOT_DIRECT_COS
-        const double cos_t12_shift = mx_cos(theta1 + theta2 - halfpi), cos_t1_shift = mx_cos(theta1 - halfpi);
-#elif MXV_ACROBOT_CARRY_ARG_ROUNDING
-        const double t12 = theta1 + theta2;
-        const double a12 = t12 - halfpi;
-        const double eps12 = kHalfPiTail - two_sum_residual(theta1, theta2, t12) - two_sum_residual(t12, -halfpi, a12);
-        const double C12 = __fma_rn(c1, c2, -(s1 * s2));
-        const double cos_t12_shift = __fma_rn(eps12, C12, S12);
-        const double a1 = theta1 - halfpi;
-        const double cos_t1_shift = __fma_rn(kHalfPiTail - two_sum_residual(theta1, -halfpi, a1), c1, s1);
-#else
-        const double cos_t12_shift = S12, cos_t1_shift = s1;   // sin(t1 + t2), sin(t1)
-#endif
+        const double cos_t12_shift = __fma_rn(s1, c2, c1 * s2), cos_t1_shift = s1;   // sin(t1 + t2), sin(t1)
         const double d1 = m1 * (lc1 * lc1) + m2 * ((l1 * l1) + (lc2 * lc2) + 2 * l1 * lc2 * c2) + I1 + I2;  // :252-257
         const double d2 = m2 * ((lc2 * lc2) + l1 * lc2 * c2) + I2;                                          // :258
         const double phi2 = m2 * lc2 * g * cos_t12_shift;                                                   // :259
@@ -933,18 +780,9 @@ struct Env<MXV_ACROBOT> {
         double s0, c0, s1, c1;
         mx_sincos<SAFE, fma3_for<MXV_ACROBOT>()>(s[0], &s0, &c0);
         mx_sincos<SAFE, fma3_for<MXV_ACROBOT>()>(s[1], &s1, &c1);
-        // cos(s[1] + s[0]) :235 from the same four values
-        [[maybe_unused]] const double t21 = s[1] + s[0];
-#if MXV_ACROBOT_DIRECT_COS
-        const double cos21 = mx_cos(t21);
-#elif MXV_ACROBOT_CARRY_ARG_ROUNDING
-        const double cos21 = __fma_rn(two_sum_residual(s[1], s[0], t21), __fma_rn(s0, c1, c0 * s1), __fma_rn(c0, c1, -(s0 * s1)));
-#else
-        const double cos21 = __fma_rn(c0, c1, -(s0 * s1));
-#endif
+        const double cos21 = __fma_rn(c0, c1, -(s0 * s1));  // cos(s[1] + s[0]) :235 from the same four values
         const double height = -c0 - cos21;
         bool term = height > 1.0;                            // :235
-#if MXV_ACROBOT_EXACT_BAND
         // Within 2^-40 of the threshold (the hot path's own error is a few 2^-52; ~1 env-step in 10^12 comes here) the mask is not
         // decided by 1.5-ulp trigonometry: the whole step is taken again as the reference writes it, on correctly rounded sin / cos
         // (mxv_exact.hpp), and THAT state, observation and mask stand.
@@ -958,7 +796,6 @@ struct Env<MXV_ACROBOT> {
             s0 = landed(scx[0]); c0 = landed(scx[1]); s1 = landed(scx[2]); c1 = landed(scx[3]);
             __builtin_amdgcn_s_waitcnt(0x0F70);
         }
-#endif
         reward = (!term) ? -1.0 : 0.0;                     // :219
         obs[0] = (float)c0; obs[1] = (float)s0; obs[2] = (float)c1; obs[3] = (float)s1;
         obs[4] = (float)s[2]; obs[5] = (float)s[3];

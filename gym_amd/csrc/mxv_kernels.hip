@@ -28,10 +28,7 @@ __device__ __forceinline__ void raise_error(int32_t *err, int32_t bit) { *reinte
 
 // The single-step launch's stores carry the nontemporal hint: nothing it writes is read again before the launch ends, and lines that do
 // not linger in the L2s shorten the write-back at the end of the kernel — step(actions) at 2^20 envs 18.8 -> 18.4 / 18.7 us in two boxes, i.e.
-// 1-2 % (on the loads the same hint COSTS 4 us: profiles/r6/r6i_step_launch_shape.md).  -DMXV_STEP_NT_STORES=0 is the A/B hook.
-#ifndef MXV_STEP_NT_STORES
-#define MXV_STEP_NT_STORES 1
-#endif
+// 1-2 % (on the loads the same hint COSTS 4 us: profiles/r6/r6i_step_launch_shape.md).
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
@@ -79,9 +76,7 @@ __device__ __forceinline__ void store_obs(float *base, int64_t e, const float *o
 // wave-step.  An empty asm on the 32-bit value pins the extension behind it: the store takes its scalar base in the instruction's saddr
 // field, `global_store_dwordx4 v_off, v[data], s[base:base+1]`, with one VGPR per offset and no address arithmetic.
 __device__ __forceinline__ uint32_t pin32(uint32_t v) {
-#if MXV_SADDR_STORES
     asm volatile("" : "+v"(v));
-#endif
     return v;
 }
 
@@ -113,22 +108,9 @@ __device__ __forceinline__ void store_obs_at(char *base, uint32_t byte_off, cons
 // low XCDs, matching how many ids of each residue exist).
 constexpr unsigned kXcds = 8;
 __device__ __forceinline__ unsigned xcd_contiguous_tile(unsigned bid, unsigned ntiles) {
-#if MXV_XCD_MAP
     const unsigned x = bid % kXcds, idx = bid / kXcds;
-#if MXV_XCD_BLOCK > 0
-    // XCDs take turns in blocks of MXV_XCD_BLOCK tiles (tuning variant; tiles past the end are skipped by the callers' bounds)
-    if (ntiles % (kXcds * MXV_XCD_BLOCK) == 0) return ((idx / MXV_XCD_BLOCK) * kXcds + x) * MXV_XCD_BLOCK + idx % MXV_XCD_BLOCK;
-#endif
     const unsigned base = ntiles / kXcds, rem = ntiles % kXcds;
     return x * base + (x < rem ? x : rem) + idx;
-#else
-    return bid;
-#endif
-}
-
-// Word `idx` (0..3, runtime) of a Philox result.
-[[maybe_unused]] __device__ __forceinline__ uint32_t pick_word(const U4 &w, uint32_t idx) {
-    return idx == 0 ? w.x : (idx == 1 ? w.y : (idx == 2 ? w.z : w.w));
 }
 
 // ---- the fp64 state as (float32, int32) pairs: "the observation carries the state" (mxv_adopt_obs, round 6) -------------------------------
@@ -228,26 +210,23 @@ __global__ void __launch_bounds__(kBlock) hilo_join_kernel(const float *hi_obs, 
     for (int k = 0; k < S; ++k) state[(int64_t)k * n + e] = hilo_decode(o[k], l[k], state + (int64_t)k * n + e);
 }
 
-// step_kernel<ENV, DEF, E, CONSEC>: a.K vector steps in ONE launch, env state held in registers between
+// step_kernel<ENV, DEF, E>: a.K vector steps in ONE launch, env state held in registers between
 // steps (K = 1 is the plain step() call).  Per step the only HBM traffic is the step's outputs; state
 // and elapsed[] are read once at entry and written once at exit, i.e. 16*S/K + 8/K bytes per env-step.
-//   CONSEC = false: lane owns envs tile0 + j*256 + tid (every access of a wave is a dense burst);
-//                   Philox action words are transposed through LDS (one call = 4 consecutive envs).
-//   CONSEC = true : lane owns the E consecutive envs tile0 + tid*E + j: a Philox action group is
-//                   lane-private (no LDS, no barrier) and the flag bytes of a lane are contiguous.
+// Lane owns envs tile0 + j*256 + tid (every access of a wave is a dense burst); Philox action words are
+// transposed through LDS (one call = 4 consecutive envs).
 //   CLOCK = true  : the launch advances the device clock itself (single steps with default parameters of a handle in device-clock mode,
 //                   small grids).  An instantiation of its own: as a run-time branch at the exit of the one kernel it cost every
 //                   launch 1.1 us per 2^20-env step (18.6 -> 19.8, profiles/r4/r4q_step_clock_tail_ab.txt).
 //   HILO = true   : the state arrives as (previous observation, int32 residual) pairs and leaves the same way (see hilo_encode above):
 //                   single steps with default parameters of a handle that adopted the caller's observation buffer.
-template <int ENV, int DEF, int E, bool CONSEC, bool MULTI, bool CLOCK = false, bool HILO = false>
-__global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepArgs a) {
+template <int ENV, int DEF, int E, bool MULTI, bool CLOCK = false, bool HILO = false>
+__global__ void __launch_bounds__(kBlock, 1) step_kernel(const StepArgs a) {
     using EV = Env<ENV>;
     constexpr int S = EV::S, O = EV::O, NA = EV::NA;
     static_assert(!HILO || (!MULTI && S == O && EV::AUX == 0), "HILO: one step, observation = float32(state)");
     constexpr int TILE = E * kBlock;
-    constexpr bool NT = !MULTI && MXV_STEP_NT_STORES != 0;
-    static_assert(!CONSEC || E == 1 || E == 2 || E % 4 == 0, "CONSEC needs E in {1, 2, 4k}");
+    constexpr bool NT = !MULTI;
     const int tid = threadIdx.x;
     const int64_t tile0 = (int64_t)xcd_contiguous_tile(blockIdx.x, gridDim.x) * TILE;
     const int64_t n = a.n;
@@ -255,7 +234,7 @@ __global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepA
     const uint64_t t0 = a.t + (a.t_dev ? *a.t_dev : 0);
     const bool autoreset = !(a.flags & MXV_FLAG_NO_AUTORESET);
     const bool sampled = a.actions == nullptr;
-    auto env_of = [&](int j) -> int64_t { return CONSEC ? tile0 + (int64_t)tid * E + j : tile0 + (int64_t)j * kBlock + tid; };
+    auto env_of = [&](int j) -> int64_t { return tile0 + (int64_t)j * kBlock + tid; };
 
     // ---- entry: state + elapsed of the lane's E envs ----
     constexpr int AUXN = EV::AUX > 0 ? EV::AUX : 1;
@@ -300,7 +279,7 @@ __global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepA
     uint32_t ep[E], ep_in[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) ep[j] = ep_in[j] = (autoreset && !LAZY_EP) ? a.episodes[valid[j] ? env_of(j) : 0] : 0u;
-    __shared__ uint32_t sw[CONSEC ? 4 : TILE];
+    __shared__ uint32_t sw[TILE];
 
     const int nsteps = MULTI ? a.K : 1;  // MULTI = false: the plain step() launch, no loop-carried bookkeeping
     if (MULTI) settle_entry_loads();
@@ -313,27 +292,16 @@ __global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepA
         int ai[E];
         float af[E];
         if (sampled) {
-            if constexpr (CONSEC) {
-#pragma unroll
-                for (int j0 = 0; j0 < E; j0 += 4) {
-                    const uint64_t ge = a.env0 + (uint64_t)env_of(j0);
-                    const U4 w = env_action_words<ENV>(a.action_seed, t, ge >> 2);
-#pragma unroll
-                    for (int q = 0; q < 4 && j0 + q < E; ++q)
-                        action_from_word<ENV, DEF>(P.at(valid[j0 + q] ? env_of(j0 + q) : 0), pick_word(w, (uint32_t)((ge + q) & 3)), t, ai[j0 + q], af[j0 + q]);
-                }
-            } else {
-                // thread c computes the 4 words of group (env0 + tile0)/4 + c; LDS hands them to the owning lanes
-                if (MULTI && step > 0) __syncthreads();
-                for (int c = tid; c < TILE / 4; c += kBlock) {
-                    const uint64_t g = ((a.env0 + (uint64_t)tile0) >> 2) + (uint64_t)c;
-                    const U4 w = env_action_words<ENV>(a.action_seed, t, g);
-                    reinterpret_cast<uint4 *>(sw)[c] = make_uint4(w.x, w.y, w.z, w.w);
-                }
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < E; ++j) action_from_word<ENV, DEF>(P.at(valid[j] ? env_of(j) : 0), sw[j * kBlock + tid], t, ai[j], af[j]);
+            // thread c computes the 4 words of group (env0 + tile0)/4 + c; LDS hands them to the owning lanes
+            if (MULTI && step > 0) __syncthreads();
+            for (int c = tid; c < TILE / 4; c += kBlock) {
+                const uint64_t g = ((a.env0 + (uint64_t)tile0) >> 2) + (uint64_t)c;
+                const U4 w = env_action_words<ENV>(a.action_seed, t, g);
+                reinterpret_cast<uint4 *>(sw)[c] = make_uint4(w.x, w.y, w.z, w.w);
             }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < E; ++j) action_from_word<ENV, DEF>(P.at(valid[j] ? env_of(j) : 0), sw[j * kBlock + tid], t, ai[j], af[j]);
             if (a.actions_out != nullptr) {
 #pragma unroll
                 for (int j = 0; j < E; ++j) {
@@ -414,7 +382,7 @@ __global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepA
                 if (pend[j]) jsel = j;
             if (!__any(jsel >= 0)) break;
             if (jsel >= 0) {
-                const int64_t e = CONSEC ? tile0 + (int64_t)tid * E + jsel : tile0 + (int64_t)jsel * kBlock + tid;
+                const int64_t e = tile0 + (int64_t)jsel * kBlock + tid;
                 bool v = false;
                 uint32_t k_reset = 0;
                 float cur[O];
@@ -475,7 +443,7 @@ __global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepA
             // store stands): a wave-uniform test of the pointer keeps every other launch off this code, and no block boundary cuts
             // through the step's arithmetic.  (In the middle of the dynamics loop the same lines cost step(actions) 22.1 -> 23.3 us
             // per 2^20-env step although they never ran: profiles/r4/r4d_step_path_ab.json.)
-            if (MXV_CARTPOLE_BEYOND && a.beyond != nullptr) {
+            if (a.beyond != nullptr) {
 #pragma unroll
                 for (int j = 0; j < E; ++j)
                     if (valid[j] && term[j]) {
@@ -547,7 +515,7 @@ __global__ void __launch_bounds__(kBlock, MXV_MIN_WAVES) step_kernel(const StepA
 //     episode starts.  Every lane keeps, per env slot, a ready-made reset entry — new fp64 state, carried aux values and the
 //     float32 observation — in a lane-private LDS slot (LDS as a register spill area: no other lane reads it).  An env that
 //     finishes step t copies its entry (three ds_read_b128 for CartPole) and marks the slot empty; empty slots are refilled by
-//     look-ahead passes, one Philox call of the lanes that need one, every MXV_ROLLOUT_PASS_PERIOD steps per slot.  CartPole
+//     look-ahead passes, one Philox call of the lanes that need one, every kRolloutPassPeriod steps per slot.  CartPole
 //     (~6 of a wave's 128 envs finish per step): 0.25 masked Philox calls + reset arithmetic per wave-step instead of 1.0;
 //     envs that only truncate (Pendulum at step 200, ...): one call per episode.  An env that finishes again before its
 //     slot was refilled (TimeLimit of a few steps) forces the pass early — any schedule gives the same bits, the words
@@ -577,7 +545,6 @@ struct alignas(16) ResetEntry<S, O, 0> {  // no carried values: CartPole's entry
 // The rarely launched instantiations (runtime parameters; CartPole right after a state injection) keep the allocator's choice.
 template <int ENV, bool DEF, bool SAFE>
 constexpr int rollout_min_waves() {
-    if (MXV_ROLLOUT_MIN_WAVES > 1) return MXV_ROLLOUT_MIN_WAVES;
     return (!DEF || (ENV == MXV_CARTPOLE && SAFE)) ? 1 : 4;
 }
 
@@ -664,7 +631,7 @@ __device__ __forceinline__ void rollout_body_v3(const StepArgs &a, const unsigne
     constexpr int NACT = TILE / 4;        // lanes that draw the action words of ONE unit (step, or 32-step block) for the tile
     constexpr int H = kWave / NACT;       // units one full-wave call produces = slots of the LDS ring
     constexpr int SH = action_unit_shift<ENV>();
-    constexpr int PERIOD = MXV_ROLLOUT_PASS_PERIOD;
+    constexpr int PERIOD = kRolloutPassPeriod;
     static_assert(NACT <= kWave && (PERIOD & (PERIOD - 1)) == 0 && PERIOD >= E, "E <= 4; pass period a power of two >= E");
     constexpr int AUXN = EV::AUX > 0 ? EV::AUX : 1;
     using Entry = ResetEntry<S, O, EV::AUX>;
@@ -797,7 +764,6 @@ __device__ __forceinline__ void rollout_body_v3(const StepArgs &a, const unsigne
     const uint32_t rew_b = rew_f32 ? 4u : 8u;
     const uint32_t act_b = (NA > 0 && !act_i32) ? 8u : 4u;
     uint32_t lo[E];  // index of the lane's env slot inside one step's slice of every output array
-#if MXV_SADDR_STORES
     // every output base is moved to this wave's tile (wave-uniform: scalar arithmetic), lanes keep an offset below E * 64 elements: the
     // byte offsets fit 32 bits whatever the shard size, which is what lets the stores use scalar-base addressing (pin32)
     const int64_t slice = a.slice;
@@ -811,12 +777,6 @@ __device__ __forceinline__ void rollout_body_v3(const StepArgs &a, const unsigne
     if (p_fin) p_fin += tile0 * (int64_t)(O * sizeof(float));
     if (p_epr) p_epr += tile0;
     if (p_epl) p_epl += tile0;
-#else
-    const int64_t slice = a.slice;
-#pragma unroll
-    for (int j = 0; j < E; ++j) lo[j] = le[j];
-#endif
-
 
     settle_entry_loads();
     // The loop exists twice in a tape-driven kernel: ALLV = every env slot of the wave is a real env (all tiles but possibly the
@@ -1315,13 +1275,10 @@ hipError_t launch_rollout_stats(const StepArgs &a, hipStream_t stream, LaunchInf
     return hipGetLastError();
 }
 
-#ifndef MXV_STEP_E1_FROM   // (A/B hook: tools/ab_step_shape.sh builds the library with this out of reach)
-#define MXV_STEP_E1_FROM ((int64_t)1 << 19)
-#endif
 // Single CartPole steps of at least this many envs run ONE env per lane: 2 x 8 waves per SIMD instead of one round of 8, so one
 // round's stores overlap the other's loads (profiles/r6/r6i_step_launch_shape.md: 19.4 -> 18.7 us at 2^20; below 2^19 the launch
 // is latency-bound and two envs per lane win).
-constexpr int64_t kStepOneEnvPerLaneFrom = MXV_STEP_E1_FROM;
+constexpr int64_t kStepOneEnvPerLaneFrom = (int64_t)1 << 19;
 
 template <int ENV>
 hipError_t launch_step_env(int pm, const StepArgs &a, hipStream_t stream, LaunchInfo *info) {
@@ -1334,7 +1291,7 @@ hipError_t launch_step_env(int pm, const StepArgs &a, hipStream_t stream, Launch
         // below 2^19), so sin/cos need no range check.  A state injection (mxv_set_state) or unusual explicit-reset bounds break
         // that for one launch; an unlimited Pendulum can turn without bound.
         const bool bounded = ENV != MXV_PENDULUM || (a.max_steps > 0 && a.max_steps < 1000000);
-        const bool fast = def && !a.state_injected && bounded && MXV_FAST_TRIG;
+        const bool fast = def && !a.state_injected && bounded;
         auto go = [&](auto er_tag) {
             constexpr int ER = decltype(er_tag)::value;
             const int64_t rtile = (int64_t)ER * kWave;
@@ -1348,19 +1305,19 @@ hipError_t launch_step_env(int pm, const StepArgs &a, hipStream_t stream, Launch
             }
         };
         // Two envs per lane (the tuned choice of the light envs: two independent chains of ILP) only pay when the shard fills
-        // the chip: below one E = 2 wave per SIMD (1024 SIMDs x 128 envs) the work is latency-bound and one env per lane
+        // the chip: up to one E = 2 wave per SIMD (1024 SIMDs x 128 envs) the work is latency-bound and one env per lane
         // puts twice as many waves on it (profiles/r2/r02a_shard_sweep.jsonl: 0.76 vs 1.05 us per step at 2^16 CartPole envs;
-        // at 2^17 itself, one E = 2 wave per SIMD: 0.92 vs 1.01, profiles/r3/r3k_small_shard_e1_ab.jsonl) — the shard sizes of an 8-GPU
+        // at 2^17 itself: CartPole 0.92 vs 1.01, MountainCar 0.75 vs 0.85, MountainCarContinuous 0.79 vs 0.99; at 2^18 two envs per
+        // lane win, 1.43 vs 1.53: profiles/r3/r3k_small_shard_e1_ab.jsonl, r3s_e1_factor_ab.jsonl) — the shard sizes of an 8-GPU
         // strong-scaling or mixed-batch job.
         constexpr int ER = rollout_envs_per_lane(ENV);
-        if (ER > 1 && a.n < (int64_t)kSimds * ER * kWave * MXV_ROLLOUT_E1_FACTOR + MXV_ROLLOUT_E1_INCLUSIVE && MXV_ROLLOUT_SMALL_E1)
+        if (ER > 1 && a.n <= (int64_t)kSimds * ER * kWave)
             go(std::integral_constant<int, 1>{});
         else
             go(std::integral_constant<int, ER>{});
         return hipGetLastError();
     }
     constexpr int E = envs_per_lane(ENV);
-    constexpr bool C = MXV_CONSEC != 0;
     const int64_t tile = (int64_t)E * kBlock;
     const unsigned grid = (unsigned)((a.n + tile - 1) / tile);
     if (info) *info = LaunchInfo{0, ENV, pm, E, 1, 0, a.actions != nullptr ? 1 : 0, a.K, grid, (uint32_t)kBlock};
@@ -1373,26 +1330,26 @@ hipError_t launch_step_env(int pm, const StepArgs &a, hipStream_t stream, Launch
         if (a.K == 1 && pm == PM_DEFAULT && a.clock_ticket == nullptr && a.n >= kStepOneEnvPerLaneFrom) {
             const unsigned grid1 = (unsigned)((a.n + kBlock - 1) / kBlock);
             if (info) *info = LaunchInfo{0, ENV, pm, 1, 1, 0, a.actions != nullptr ? 1 : 0, a.K, grid1, (uint32_t)kBlock};
-            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, 1, C, false>), dim3(grid1), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, 1, false>), dim3(grid1), dim3(kBlock), 0, stream, a);
             return hipGetLastError();
         }
     }
     if (a.K > 1) {
         if (pm == PM_DEFAULT)
-            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, C, true>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, true>), dim3(grid), dim3(kBlock), 0, stream, a);
         else if (pm == PM_BROADCAST)
-            hipLaunchKernelGGL((step_kernel<ENV, PM_BROADCAST, E, C, true>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_BROADCAST, E, true>), dim3(grid), dim3(kBlock), 0, stream, a);
         else
-            hipLaunchKernelGGL((step_kernel<ENV, PM_PER_ENV, E, C, true>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_PER_ENV, E, true>), dim3(grid), dim3(kBlock), 0, stream, a);
     } else {
         if (pm == PM_DEFAULT && a.clock_ticket != nullptr)
-            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, C, false, true>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, false, true>), dim3(grid), dim3(kBlock), 0, stream, a);
         else if (pm == PM_DEFAULT)
-            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, C, false>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, false>), dim3(grid), dim3(kBlock), 0, stream, a);
         else if (pm == PM_BROADCAST)
-            hipLaunchKernelGGL((step_kernel<ENV, PM_BROADCAST, E, C, false>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_BROADCAST, E, false>), dim3(grid), dim3(kBlock), 0, stream, a);
         else
-            hipLaunchKernelGGL((step_kernel<ENV, PM_PER_ENV, E, C, false>), dim3(grid), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_PER_ENV, E, false>), dim3(grid), dim3(kBlock), 0, stream, a);
     }
     return hipGetLastError();
 }
@@ -1417,19 +1374,18 @@ bool hilo_supported(int env_id) { return env_id == MXV_CARTPOLE || env_id == MXV
 template <int ENV>
 static hipError_t launch_hilo_step_env(const StepArgs &a, hipStream_t stream, LaunchInfo *info) {
     constexpr int E = envs_per_lane(ENV);
-    constexpr bool C = MXV_CONSEC != 0;
     if constexpr (ENV == MXV_CARTPOLE && E > 1) {      // (two rounds instead of one: see launch_step_env)
         if (a.n >= kStepOneEnvPerLaneFrom) {
             const unsigned grid1 = (unsigned)((a.n + kBlock - 1) / kBlock);
             if (info) *info = LaunchInfo{0, ENV, PM_DEFAULT, 1, 1, 3, a.actions != nullptr ? 1 : 0, 1, grid1, (uint32_t)kBlock};
-            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, 1, C, false, false, true>), dim3(grid1), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, 1, false, false, true>), dim3(grid1), dim3(kBlock), 0, stream, a);
             return hipGetLastError();
         }
     }
     const int64_t tile = (int64_t)E * kBlock;
     const unsigned grid = (unsigned)((a.n + tile - 1) / tile);
     if (info) *info = LaunchInfo{0, ENV, PM_DEFAULT, E, 1, 3 /* out_mode 3: the observation carries the state */, a.actions != nullptr ? 1 : 0, 1, grid, (uint32_t)kBlock};
-    hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, C, false, false, true>), dim3(grid), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL((step_kernel<ENV, PM_DEFAULT, E, false, false, true>), dim3(grid), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 hipError_t launch_hilo_step(int env_id, const StepArgs &a, hipStream_t stream, LaunchInfo *info) {
@@ -1473,7 +1429,7 @@ bool launch_step_is_rollout(int pm, const StepArgs &a) {
 // every per-step output present and one dtype set — and always with the env kind's own envs-per-lane, so that the leaves of the sum
 // tree (one per tile) are the same however small the shard is.
 bool launch_step_supports_stats(int env_id, int pm, const StepArgs &a) {
-    if (!launch_step_is_rollout(pm, a) || pm != PM_DEFAULT || a.actions != nullptr || a.state_injected || !MXV_FAST_TRIG) return false;
+    if (!launch_step_is_rollout(pm, a) || pm != PM_DEFAULT || a.actions != nullptr || a.state_injected) return false;
     if (env_id == MXV_PENDULUM && !(a.max_steps > 0 && a.max_steps < 1000000)) return false;
     if (!(a.reward && a.actions_out && a.terminated && a.truncated && !a.final_obs && !a.ep_acc) || a.slice == 0) return false;
     const int f = a.flags & (MXV_FLAG_REWARD_F32 | MXV_FLAG_ACTION_I32);

@@ -111,89 +111,14 @@ struct SampleArgs {
 // Envs per lane of the step kernel (tile = E * 256 envs per workgroup), chosen per env kind from the sweep in
 // profiles/r1/r01_variant_sweep.md: two interleaved chains for the light envs (ILP without register spills; four
 // chains spill SGPRs/VGPRs inside the fused loop), one chain for Pendulum and for Acrobot's RK4 (~60 live fp64).
-#ifndef MXV_ENVS_PER_LANE
-#define MXV_ENVS_PER_LANE 2
-#endif
-#ifndef MXV_ENVS_PER_LANE_PENDULUM
-#define MXV_ENVS_PER_LANE_PENDULUM 1
-#endif
-#ifndef MXV_ENVS_PER_LANE_ACROBOT
-#define MXV_ENVS_PER_LANE_ACROBOT 1
-#endif
-constexpr int envs_per_lane(int env_id) {
-    return env_id == MXV_ACROBOT ? MXV_ENVS_PER_LANE_ACROBOT
-                                 : (env_id == MXV_PENDULUM ? MXV_ENVS_PER_LANE_PENDULUM : MXV_ENVS_PER_LANE);
-}
+// Indexed by env id (include/mxv.h: CartPole, Pendulum, Acrobot, MountainCar, MountainCarContinuous).
+constexpr int kStepEnvsPerLane[MXV_NUM_ENV_KINDS] = {2, 1, 1, 2, 2};
+constexpr int envs_per_lane(int env_id) { return kStepEnvsPerLane[env_id]; }
 // Envs per lane of rollout_kernel (one wave64 per workgroup, tile = E * 64 envs; E <= 3).
-#ifndef MXV_ROLLOUT_E
-#define MXV_ROLLOUT_E 2
-#endif
-#ifndef MXV_ROLLOUT_E_PENDULUM
-#define MXV_ROLLOUT_E_PENDULUM 1
-#endif
-#ifndef MXV_ROLLOUT_E_ACROBOT
-#define MXV_ROLLOUT_E_ACROBOT 1
-#endif
-#ifndef MXV_ROLLOUT_E_MOUNTAINCAR
-#define MXV_ROLLOUT_E_MOUNTAINCAR MXV_ROLLOUT_E
-#endif
-#ifndef MXV_ROLLOUT_E_MOUNTAINCAR_CONT
-#define MXV_ROLLOUT_E_MOUNTAINCAR_CONT MXV_ROLLOUT_E
-#endif
-constexpr int rollout_envs_per_lane(int env_id) {
-    return env_id == MXV_ACROBOT ? MXV_ROLLOUT_E_ACROBOT
-           : env_id == MXV_PENDULUM ? MXV_ROLLOUT_E_PENDULUM
-           : env_id == MXV_MOUNTAINCAR ? MXV_ROLLOUT_E_MOUNTAINCAR
-           : env_id == MXV_MOUNTAINCAR_CONT ? MXV_ROLLOUT_E_MOUNTAINCAR_CONT
-                                            : MXV_ROLLOUT_E;
-}
-// 1: a lane owns E consecutive envs (lane-private Philox action group); 0: wave-dense striding + LDS exchange.
-#ifndef MXV_CONSEC
-#define MXV_CONSEC 0
-#endif
-// __launch_bounds__ second argument = minimum waves per SIMD (4 => at most 128 VGPRs): a 2^20-env launch at 4 envs
-// per lane is exactly 4 waves per SIMD, all of which must be co-resident to run in one round.
-#ifndef MXV_MIN_WAVES
-#define MXV_MIN_WAVES 1
-#endif
-// 1: shards smaller than one E-env-per-lane wave per SIMD run the fused rollout with one env per lane (A/B hook)
-#ifndef MXV_ROLLOUT_SMALL_E1
-#define MXV_ROLLOUT_SMALL_E1 1
-#endif
-// the shard size below which a two-envs-per-lane kind runs one env per lane: FACTOR x (one E = 2 wave per SIMD); INCLUSIVE = 1 includes
-// the boundary itself, i.e. the 2^17-env shard of an 8-GPU strong-scaling job (round 3: 1.01 -> 0.92 us per CartPole step, MountainCar
-// 0.85 -> 0.75, MountainCarContinuous 0.99 -> 0.79; at 2^18 two envs per lane win, 1.43 vs 1.53, at 2^19 the two are equal.  profiles/r3/r3k_small_shard_e1_ab.jsonl, r3s_e1_factor_ab.jsonl)
-#ifndef MXV_ROLLOUT_E1_FACTOR
-#define MXV_ROLLOUT_E1_FACTOR 1
-#endif
-#ifndef MXV_ROLLOUT_E1_INCLUSIVE
-#define MXV_ROLLOUT_E1_INCLUSIVE 1
-#endif
+constexpr int kRolloutEnvsPerLane[MXV_NUM_ENV_KINDS] = {2, 1, 1, 2, 2};
+constexpr int rollout_envs_per_lane(int env_id) { return kRolloutEnvsPerLane[env_id]; }
 // steps between two look-ahead passes of rollout_kernel_v3 over the same env slot (power of two, >= envs per lane)
-#ifndef MXV_ROLLOUT_PASS_PERIOD
-#define MXV_ROLLOUT_PASS_PERIOD 8
-#endif
-// rollout_kernel's minimum waves per SIMD (tuning hook; 1 = let the register allocator decide: 113 VGPRs = 4 waves for CartPole)
-#ifndef MXV_ROLLOUT_MIN_WAVES
-#define MXV_ROLLOUT_MIN_WAVES 1
-#endif
-// 1: the fused rollout's stores take a wave-uniform scalar base + a pinned 32-bit lane offset (pin32 in mxv_kernels.hip); 0: round 2's
-// 64-bit vector addresses (A/B hook)
-#ifndef MXV_SADDR_STORES
-#define MXV_SADDR_STORES 1
-#endif
-// A/B hook: 0 compiles CartPole's steps_beyond_terminated bookkeeping out of step_kernel
-#ifndef MXV_CARTPOLE_BEYOND
-#define MXV_CARTPOLE_BEYOND 1
-#endif
-// 1: XCD-aware workgroup -> tile map (see xcd_contiguous_tile in mxv_kernels.hip); 0: tiles in workgroup-id order.
-#ifndef MXV_XCD_MAP
-#define MXV_XCD_MAP 1
-#endif
-// > 0: the XCD-aware map hands each XCD blocks of this many tiles in turn instead of one contiguous eighth (tuning hook)
-#ifndef MXV_XCD_BLOCK
-#define MXV_XCD_BLOCK 0
-#endif
+constexpr int kRolloutPassPeriod = 8;
 constexpr int kBlock = 256;
 
 // Which kernel instantiation a step launch took (mxv_last_launch, include/mxv.h: mxv_launch_info has the same members)

@@ -44,16 +44,6 @@ constexpr int kRewLeafEnvs = 256;   // envs per leaf of the return-sum tree (one
 constexpr int kTreeFan = 1024;      // leaves folded per workgroup per tree level (a complete 10-level subtree)
 constexpr int kMaxWorld = 64;
 
-#ifndef MXV_NORM_DPP_REDUCE
-#define MXV_NORM_DPP_REDUCE 1  // A/B hook: 0 = the six ds_bpermute stages of __shfl_xor
-#endif
-#ifndef MXV_NORM_XCD_MAP
-#define MXV_NORM_XCD_MAP 1     // A/B hook: 0 = leaf = workgroup id
-#endif
-#ifndef MXV_NORM_VEC4
-#define MXV_NORM_VEC4 1        // A/B hook: 0 = lane L of a return leaf owns envs L, L + 64, L + 128, L + 192 (twelve loads per step)
-#endif
-
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
@@ -62,12 +52,11 @@ __device__ __forceinline__ double dpp_f64(double v) {
 }
 
 __device__ __forceinline__ double wave_tree_sum(double v) {
-    // xor butterfly = the binary tree over lane index (addition is commutative, so every lane holds the tree's value)
-#if MXV_NORM_DPP_REDUCE
-    // The same tree without LDS round trips.  Stages 1, 2: quad permutes (lane ^ 1, lane ^ 2).  Stages 4, 8: after them every lane of
-    // a quad (of a half row) holds the same partial sum, so the mirror permutes of the DPP unit — lane 7 - i of the half row, lane
-    // 15 - i of the row — deliver what lane ^ 4 (lane ^ 8) holds.  Stages 16, 32: gfx950's v_permlane16_swap / v_permlane32_swap.
-    // a + b == b + a exactly, so the value is the __shfl_xor butterfly's, bit for bit.
+    // xor butterfly = the binary tree over lane index (addition is commutative, so every lane holds the tree's value), without LDS round
+    // trips (__shfl_xor's six ds_bpermute stages: slower, profiles/r4/r4n_normalize_variants.txt).  Stages 1, 2: quad permutes (lane ^ 1,
+    // lane ^ 2).  Stages 4, 8: after them every lane of a quad (of a half row) holds the same partial sum, so the mirror permutes of the
+    // DPP unit — lane 7 - i of the half row, lane 15 - i of the row — deliver what lane ^ 4 (lane ^ 8) holds.  Stages 16, 32: gfx950's
+    // v_permlane16_swap / v_permlane32_swap.  a + b == b + a exactly, so the value is the __shfl_xor butterfly's, bit for bit.
     v += dpp_f64<0xB1>(v);    // quad_perm [1, 0, 3, 2]
     v += dpp_f64<0x4E>(v);    // quad_perm [2, 3, 0, 1]
     v += dpp_f64<0x141>(v);   // row_half_mirror
@@ -82,10 +71,6 @@ __device__ __forceinline__ double wave_tree_sum(double v) {
         const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
         v = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);   // lower half + upper half
     }
-#else
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-#endif
     return v;
 }
 
@@ -160,7 +145,6 @@ __global__ void __launch_bounds__(64) returns_sums_kernel(const RT *__restrict__
                                                           int64_t n, int K, double gamma, int64_t leaves,
                                                           double *__restrict__ partials, int aligned) {
     const int lane = threadIdx.x;
-#if MXV_NORM_XCD_MAP
     // workgroup ids are dealt round-robin over the 8 XCDs: XCD x takes the x-th contiguous eighth of the leaves (as the rollout kernels'
     // tiles), so that the lines one L2 fetches at a step are neighbours in memory
     int64_t leaf;
@@ -168,15 +152,12 @@ __global__ void __launch_bounds__(64) returns_sums_kernel(const RT *__restrict__
         const unsigned bid = blockIdx.x, nb = gridDim.x, x = bid % 8u, idx = bid / 8u, base = nb / 8u, rem = nb % 8u;
         leaf = (int64_t)(x * base + (x < rem ? x : rem) + idx);
     }
-#else
-    const int64_t leaf = blockIdx.x;
-#endif
     int64_t e[4];
     bool live[4];
     double ret[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        e[j] = MXV_NORM_VEC4 ? leaf * kRewLeafEnvs + 4 * lane + j : leaf * kRewLeafEnvs + j * 64 + lane;
+        e[j] = leaf * kRewLeafEnvs + 4 * lane + j;
         live[j] = e[j] < n;
         ret[j] = live[j] ? returns[e[j]] : 0.0;
     }
@@ -194,7 +175,7 @@ __global__ void __launch_bounds__(64) returns_sums_kernel(const RT *__restrict__
     };
     Slot ring[D];
     // wave-uniform: the whole leaf exists and every step of the [K][n] tensors starts on a multiple of four elements
-    const bool vec = MXV_NORM_VEC4 && aligned && (n & 3) == 0 && (leaf + 1) * kRewLeafEnvs <= n;   // aligned: the host checked the tensors' addresses
+    const bool vec = aligned && (n & 3) == 0 && (leaf + 1) * kRewLeafEnvs <= n;   // aligned: the host checked the tensors' addresses
     auto run = [&](auto vec_tag) __attribute__((always_inline)) {
         constexpr bool VEC = decltype(vec_tag)::value;
         auto fetch = [&](int k, Slot &sl) {

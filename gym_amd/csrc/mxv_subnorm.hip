@@ -90,9 +90,6 @@ __device__ __forceinline__ void store_row(double *base, int64_t row, const doubl
 // (a dividend outside 2^-723 .. 2^677, a divisor outside 2^-64 .. 2^64 — v_div_scale rescales when the dividend's exponent is tiny, the
 // exponents differ by 768 or more, or the quotient would be subnormal — i.e. statistics somebody injected, never the dynamics) send the
 // WAVE down the plain `/` path, so the result is IEEE division bit for bit everywhere; tests/test_gpu_subnorm.py walks both paths.
-#ifndef MXV_SUBNORM_SHARED_RCP
-#define MXV_SUBNORM_SHARED_RCP 1   // A/B hook: 0 = the compiler's `/` everywhere
-#endif
 // (v_frexp_exp_i32_f64 answers 0 for zero, Inf and NaN — v_div_fixup's business, accepted — and the true exponent for subnormals: one
 // instruction, an add and an unsigned compare per test.)
 __device__ __forceinline__ bool plain_operand(double x) {   // finite non-zero needs 2^-723 <= |x| < 2^678
@@ -129,7 +126,7 @@ __device__ __forceinline__ void update_one(const float (&x)[D], double (&mean)[D
         sq[j] = (delta[j] * delta[j]) * count;                       // :42   square(delta) * count (* 1)
         ok = ok && plain_delta(delta[j]);
     }
-    if (MXV_SUBNORM_SHARED_RCP && __all(ok)) {
+    if (__all(ok)) {
         const double r = refined_rcp(tot);
         double m2[D];
         bool ok2 = true;
@@ -253,7 +250,7 @@ __global__ void __launch_bounds__(kThreads) subnorm_rew_kernel(const SubRewArgs 
         {                                                           // :144 return_rms.update(self.returns): a batch of one (update_one)
             const double tot = count + 1.0, delta = ret - mean, sq = (delta * delta) * count;
             const bool ok = plain_divisor(tot) && (plain_divisor(count) || count == 0.0) && plain_delta(delta);
-            if (MXV_SUBNORM_SHARED_RCP && __all(ok)) {
+            if (__all(ok)) {
                 const double rc = refined_rcp(tot);
                 const double m2 = var * count + div_shared(sq, tot, rc);
                 mean = mean + div_shared(delta, tot, rc);

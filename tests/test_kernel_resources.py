@@ -290,3 +290,19 @@ def test_acrobot_building_blocks_keep_their_instruction_budget(tmp_path):
     d, s = valu("_Z6k_dsdtPKdPd"), valu("_Z8k_sincosPKdPd")
     assert d.count("v_rcp_f64_e32") == 2 and not any(i.startswith(("v_div_scale", "v_div_fmas")) for i in d) and len(d) <= 64, (len(d), d.count("v_rcp_f64_e32"))
     assert len(s) <= 54 and "scratch_" not in asm, len(s)
+
+
+def test_kernel_sources_test_no_ab_switches():
+    """The kernels hold the measured form only: a `-D` switch between the shipped code and a losing alternative is deleted with the
+    alternative (the measurements stay under profiles/).  What a preprocessor conditional may still test on an MXV_ name: the opt-in
+    parity build MXV_PENDULUM_GLIBC_POWF and mxv_exact.hpp's three portability macros (the file also compiles on the host for the tests)."""
+    csrc = os.path.join(ROOT, "gym_amd", "csrc")
+    tested = set()
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".hpp", ".cpp")):
+            with open(os.path.join(csrc, name)) as f:
+                for line in f:
+                    m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+                    if m:
+                        tested |= set(re.findall(r"\bMXV_\w+", m.group(1).split("//")[0]))
+    assert tested == {"MXV_PENDULUM_GLIBC_POWF", "MXV_XFN", "MXV_XCONST", "MXV_XCOLD"}, sorted(tested)

@@ -1,14 +1,15 @@
 #!/usr/bin/env bash
-# Builds libmxv tuning variants into gym_amd/_lib/variants/.  Spec: name:E:E_acrobot:consec:minwaves[:extra -D flags]
+# Builds libmxv variants with extra compile flags into gym_amd/_lib/variants/libmxv_<name>.so.  Spec: name:flags
+#   tools/build_variants.sh p:-DMXV_PENDULUM_GLIBC_POWF=1
 set -uo pipefail
 root="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 out="$root/gym_amd/_lib/variants"
 mkdir -p "$out"
 for s in "$@"; do
-  IFS=: read -r name e ea c mw extra <<<"$s"
+  IFS=: read -r name extra <<<"$s"
   (
     tmp="$(mktemp -d)"
-    F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -DMXV_ENVS_PER_LANE=$e -DMXV_ENVS_PER_LANE_ACROBOT=$ea -DMXV_CONSEC=$c -DMXV_MIN_WAVES=$mw $extra"
+    F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math $extra"
     /opt/rocm/bin/hipcc $F -c "$root/gym_amd/csrc/mxv_kernels.hip" -o "$tmp/k.o" 2>/dev/null &&
     /opt/rocm/bin/hipcc $F -c "$root/gym_amd/csrc/mxv_api.cpp" -o "$tmp/a.o" &&
     /opt/rocm/bin/hipcc $F -c "$root/gym_amd/csrc/mxv_norm.hip" -o "$tmp/n.o" 2>/dev/null &&

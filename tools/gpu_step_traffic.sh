@@ -2,14 +2,14 @@
 # What does a step(actions) launch really move?  A/B of the loop (default vs MXV_ELAPSED32=1, alternating in ONE box), then
 # separate --pmc FETCH_SIZE / WRITE_SIZE passes (kernel-trace only) over 200 bare launches in both dtype sets, calibrated on tools/calib.
 #   tools/gpu_step_traffic.sh <tag>          -> gpurun_out/<tag>/{ab.jsonl,traffic.json}        (profiles/r6/r6b_*)
-#   tools/gpu_step_traffic.sh <tag> shape    the four forms of the step instead (ordinary, compact, observation carries the state, both);
-#                                            the A/B is tools/ab_step_shape.sh's                        (profiles/r6/r6i_*)
+#   tools/gpu_step_traffic.sh <tag> shape    the four forms of the step instead (ordinary, compact, observation carries the state, both),
+#                                            each also timed by tools/step_loop.py                     (profiles/r6/r6i_*)
 R=${1:-r6b}; MODE=${2:-elapsed}; O=$GRAFT_REPO_ROOT/gpurun_out/$R; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 [ -x tools/calib ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o tools/calib tools/calib.hip
 if [ $MODE = shape ]; then
   VARIANTS="ref compact obs compactobs"
-  bash tools/ab_step_shape.sh > $O/ab.jsonl 2> $O/ab.err
+  for f in "" "--compact" "--obs-state" "--compact --obs-state"; do python tools/step_loop.py --envs 1048576 --steps 400 $f >> $O/ab.jsonl 2>> $O/ab.err; done
 else
   VARIANTS="ref ref32 compact compact32"
   for rep in 1 2 3; do
