@@ -1,0 +1,75 @@
+"""ctypes binding of include/mxv_render.h: rgb_array frames of the classic-control envs, drawn on the device.
+
+The header is optional (mxv.h does not include it), so its symbols are bound here, over the same library as gym_amd._native, and are
+not part of _native.EXPORTS.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native
+
+RENDER_EXPORTS = ("mxv_render_dims", "mxv_render", "mxv_render_host", "mxv_render_scene_host")
+RECORD_INTS = 12
+MAX_RECORDS = 112
+# frames per second of the reference's metadata (cartpole.py:89, acrobot.py:96, mountain_car.py:100, continuous_mountain_car.py:105)
+RENDER_FPS = {_native.CARTPOLE: 50, _native.ACROBOT: 15, _native.MOUNTAINCAR: 30, _native.MOUNTAINCAR_CONT: 30}
+PENDULUM_REASON = ("Pendulum-v1 has no rgb_array frames on the device engine: its frame blits the reference's image asset "
+                   "(assets/clockwise.png, pendulum.py:228-244), which the engine does not carry")
+
+lib = _native.lib
+lib.mxv_render_dims.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+lib.mxv_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+lib.mxv_render_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+lib.mxv_render_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+for _name in RENDER_EXPORTS:
+    getattr(lib, _name).restype = C.c_int
+
+
+def dims(env_id: int):
+    """(H, W) of an env kind's frame; NotImplementedError for Pendulum."""
+    h, w = C.c_int32(), C.c_int32()
+    rc = lib.mxv_render_dims(int(env_id), C.byref(h), C.byref(w))
+    if rc == _native.ERR_UNSUPPORTED:
+        raise NotImplementedError(PENDULUM_REASON)
+    if rc != _native.OK:
+        raise _native.MxvError(rc, f"unknown env_id {env_id}")
+    return h.value, w.value
+
+
+def _indices_host(handle, indices):
+    if indices is None:
+        return None, handle.num_envs
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    if idx.size and (idx.min() < -(2 ** 31) or idx.max() >= 2 ** 31):
+        raise IndexError("env index out of range")
+    return idx.astype(np.int32), idx.size
+
+
+def render_host(handle, indices=None) -> np.ndarray:
+    """uint8 (k, H, W, 3) frames of envs `indices` (all when None) in host memory.  Synchronises."""
+    H, W = dims(handle.env_id)
+    idx, k = _indices_host(handle, indices)
+    out = np.empty((k, H, W, 3), np.uint8)
+    if k == 0:
+        return out
+    handle._check(lib.mxv_render_host(handle._h, None if idx is None else idx.ctypes.data, k, out.ctypes.data))
+    return out
+
+
+def scene_host(handle, indices=None) -> np.ndarray:
+    """int32 (k, MAX_RECORDS, RECORD_INTS): the integer draw lists the device computes for those frames.  Synchronises."""
+    dims(handle.env_id)
+    idx, k = _indices_host(handle, indices)
+    out = np.zeros((k, MAX_RECORDS, RECORD_INTS), np.int32)
+    handle._check(lib.mxv_render_scene_host(handle._h, None if idx is None else idx.ctypes.data, k, out.ctypes.data))
+    return out
+
+
+def render_device(handle, frames, indices=None, count=None):
+    """Frames into the device tensor `frames` (uint8 [count, H, W, 3]); `indices` an int32 device tensor or None.  Stream-ordered on the
+    handle's stream, no synchronisation."""
+    k = int(count if count is not None else (indices.numel() if indices is not None else handle.num_envs))
+    handle._check(lib.mxv_render(handle._h, None if indices is None else indices.data_ptr(), k, frames.data_ptr()))

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mxv_kernels.hpp"
+#include "mxv_render.hpp"
 
 using namespace mxv;
 
@@ -189,6 +190,8 @@ int check_latched(mxv_handle *h) {
         MXV_HIP(h, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
         if (e & 1)
             return fail(h, MXV_ERR_INVALID_ACTION, "discrete action outside [0, %d) (Discrete.contains assert)", h->NA);
+        if (e & kRenderIndexErrorBit)
+            return fail(h, MXV_ERR_INVALID_ARG, "render: env index outside [0, %lld) (its frame was written as zeros)", (long long)h->cfg.num_envs);
         return fail(h, MXV_ERR_INVALID_ARG, "kernel error word 0x%x", e);
     }
     return MXV_OK;
@@ -1843,3 +1846,23 @@ int mxv_comm_stream(mxv_handle *h, void **stream) {
 }
 
 }  // extern "C"
+
+// -- what mxv_render.hip reads of a handle ------------------------------------------------------------------------------------------
+namespace mxv {
+
+int render_view(mxv_handle *h, RenderView *v) {
+    if (int rc = use_device(h)) return rc;
+    if (int rc = ensure_f64(h)) return rc;
+    v->env_id = h->cfg.env_id;
+    v->n = h->cfg.num_envs;
+    v->stream = h->stream;
+    v->state = h->state;
+    v->params_pe = h->params_pe;
+    std::memcpy(v->P, h->P.p, sizeof v->P);
+    v->err = h->err;
+    return MXV_OK;
+}
+
+int render_fail(mxv_handle *h, int code, const char *message) { return fail(h, code, "%s", message); }
+
+}  // namespace mxv

@@ -38,6 +38,13 @@ def make_vector(id: str, num_envs=None, time_limit=None, **kwargs):
         from .registration import registry as classic
         from .single_env import HipEnv, HipToyTextEnv
 
+        if kwargs.get("render_mode") == "rgb_array_list" and id in classic:
+            # what gym.make does for the reference's envs (registration.py:616-620, 689): an "rgb_array" env inside the reference's
+            # own RenderCollection.  It cannot do it here: this entry point is a function, with no `metadata` to read the modes from
+            from gym.wrappers import RenderCollection
+
+            kwargs["render_mode"] = "rgb_array"
+            return RenderCollection(as_reference_env(HipEnv(id, **kwargs)))
         return as_reference_env(HipEnv(id, **kwargs) if id in classic else HipToyTextEnv(id, **kwargs))
     from .vector_env import make
 

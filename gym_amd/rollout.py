@@ -116,6 +116,26 @@ class DeviceRollout:
         self._last = (self.obs, self.reward, self.terminated, self.truncated)
         return self._last
 
+    def render(self, indices: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rgb_array frames of the current states, drawn on the device: torch.uint8 [k, H, W, 3].  `indices`: an int32
+        device tensor of env indices (all envs when None; repeats allowed); `out`: a contiguous uint8 device tensor of that shape to
+        write into (allocated on the engine's stream when None).  Ordered after the last step on the engine's stream, no host
+        synchronisation; recordable into a torch.cuda.graph like step() (pass `out` so that the graph keeps writing one tensor).  An index
+        outside [0, num_envs) yields an all-zero frame and an error at the next synchronising call."""
+        from . import _render
+
+        H, W = _render.dims(self.spec.kind)
+        if indices is not None:
+            assert indices.is_cuda and indices.dtype == torch.int32 and indices.is_contiguous() and indices.dim() == 1
+        k = self.num_envs if indices is None else indices.numel()
+        if out is None:
+            with torch.cuda.stream(self.stream):
+                out = torch.empty((k, H, W, 3), dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (k, H, W, 3)
+        self._order_after_caller()
+        _render.render_device(self.handle, out, indices, k)
+        return out
+
     def enable_graph_capture(self, on: bool = True):
         """Make this engine's calls recordable into a hipGraph of the CALLER's (torch.cuda.graph, hipStreamBeginCapture): the vector-step
         index moves into device memory and advances on the stream (mxv_set_device_clock), so that a replayed graph continues the

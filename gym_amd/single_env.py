@@ -116,14 +116,26 @@ class _OneOfTheEngine(Env):
 
 class HipEnv(_OneOfTheEngine):
     def __init__(self, id: str, *, device: int = 0, max_episode_steps: Optional[int] = None, render_mode=None, **kwargs):
-        if render_mode is not None:
-            raise NotImplementedError("the device engine has no renderer (render_mode must be None)")
-        self._vec = HipVectorEnv(id, 1, device=device, max_episode_steps=max_episode_steps, autoreset=False, copy=True, **kwargs)
+        self._vec = HipVectorEnv(id, 1, device=device, max_episode_steps=max_episode_steps, autoreset=False, copy=True,
+                                 render_mode=render_mode, **kwargs)
+        self._surface()
+        self.closed = False
+
+    def _surface(self):
         self.spec = self._vec.spec
         self.observation_space = self._vec.single_observation_space
         self.action_space = self._vec.single_action_space
         self._discrete = self._vec._discrete
-        self.closed = False
+        self.render_mode = self._vec.render_mode
+        self.metadata = self._vec.metadata   # {"render_modes": ["rgb_array"], "render_fps": the reference's} for the renderable ids
+
+    def render(self):
+        """render_mode="rgb_array": the current frame, np.uint8 (H, W, 3) (cartpole.py:209-304 and the like), drawn on the device;
+        None before the first reset() (the reference returns None while `state is None`) and with render_mode=None."""
+        self._assert_open()
+        if self.render_mode is None or not self._vec._was_reset:
+            return None
+        return self._vec.render_frames()[0]
 
     # -- gym.Env --------------------------------------------------------------------------------------------------------------------
     def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):
@@ -171,10 +183,7 @@ class HipEnv(_OneOfTheEngine):
 
     def __setstate__(self, d):
         self.__dict__.update(d)
-        self.spec = self._vec.spec
-        self.observation_space = self._vec.single_observation_space
-        self.action_space = self._vec.single_action_space
-        self._discrete = self._vec._discrete
+        self._surface()
 
 
 class HipToyTextEnv(_OneOfTheEngine):
@@ -188,7 +197,8 @@ class HipToyTextEnv(_OneOfTheEngine):
 
     def __init__(self, id: str, *, render_mode=None, **kwargs):
         if render_mode is not None:
-            raise NotImplementedError("the device engine has no renderer (render_mode must be None)")
+            raise NotImplementedError("the toy_text engines have no frames on the device (their frames are sprite images; "
+                                      "render_mode must be None)")
         from .vector_env import make
 
         self._vec = make(id, 1, **kwargs)

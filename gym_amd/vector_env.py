@@ -289,6 +289,9 @@ class HipVectorEnv(VectorEnv):
         self._max_episode_steps = -1 if limit is None else int(limit)
         self._discrete = isinstance(action_space, Discrete)
         entropy = int.from_bytes(os.urandom(8), "little")  # Env.reset(seed=None) = fresh OS entropy (seeding.py:24)
+        render_mode = kwargs.pop("render_mode", None)
+        if render_mode is not None:      # checked before any device work: "human" and Pendulum are refused without a GPU too
+            self._enable_render(render_mode)
         # autoreset=False (MXV_FLAG_NO_AUTORESET): dynamics + TimeLimit only, a finished env stays finished until reset() — the single-env
         # contract of gym.Env (gym/core.py:75-184), which gym_amd.single_env.HipEnv builds on
         self.autoreset = bool(autoreset)
@@ -303,11 +306,32 @@ class HipVectorEnv(VectorEnv):
         self._own_arrays = self.copy or self._packed     # step/reset return arrays nobody else writes to
         allowed = CTOR_KWARGS.get(self.kind, {})
         for k, v in kwargs.items():
-            if k == "render_mode" and v is None:
-                continue
             if k not in allowed:
                 raise TypeError(f"{id} got an unexpected keyword argument {k!r}")
             self._set_param(allowed[k], v)
+
+    # -- frames (render_mode="rgb_array") ------------------------------------------------
+    def _enable_render(self, render_mode):
+        from . import _render
+
+        if render_mode != "rgb_array":
+            raise ValueError(f"render_mode={render_mode!r} is not supported by the device engine: it draws frames as arrays, "
+                             "use render_mode='rgb_array' (or 'rgb_array_list' through gym.make); 'human' needs a window")
+        fps = _render.RENDER_FPS.get(self.kind)
+        if fps is None:
+            raise NotImplementedError(_render.PENDULUM_REASON)
+        self.render_mode = "rgb_array"
+        self.metadata = {"render_modes": ["rgb_array"], "render_fps": fps}
+
+    def render_frames(self, indices=None) -> np.ndarray:
+        """np.uint8 (k, H, W, 3): the frames of sub-envs `indices` (all when None) as their render() would return them, drawn on the
+        device in one launch and copied back."""
+        self._assert_is_running()
+        if self.render_mode is None:
+            raise NotImplementedError("render_frames() needs render_mode='rgb_array' at construction")
+        from . import _render
+
+        return _render.render_host(self._handle, indices)
 
     # -- parameters (get_attr / set_attr / call) ---------------------------------------------------
     def _param_index(self, name: str) -> int:
@@ -343,6 +367,8 @@ class HipVectorEnv(VectorEnv):
         self._assert_is_running()
         if name in READ_ONLY_CALLS and not args and not kwargs:
             return self._read_only_call(name)
+        if name == "render" and self.render_mode is not None and not args and not kwargs:
+            return tuple(self.render_frames())
         if args or kwargs or name in ("step", "reset", "render", "close", "seed"):
             raise NotImplementedError(
                 f"call({name!r}, ...): sub-environment METHODS are not callable on the device engine (there are no Python sub-envs); "
@@ -381,7 +407,7 @@ class HipVectorEnv(VectorEnv):
         if name == "spec":
             return (self.spec,) * n
         if name == "render_mode":
-            return (None,) * n
+            return (self.render_mode,) * n
         if name == "action_space":
             return (self.single_action_space,) * n
         return (self.single_observation_space,) * n
