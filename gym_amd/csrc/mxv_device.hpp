@@ -12,6 +12,7 @@
 
 #include "../../include/mxv.h"
 #include "../../include/mxv_diag.h"
+#include "mxv_divide.hpp"
 
 #define MXV_XFN __device__ inline
 #define MXV_XCONST __device__ const
@@ -216,28 +217,15 @@ __device__ __forceinline__ double div_by_const(double x, double c, double rc) {
     const double r = __fma_rn(-c, q0, x);
     return __fma_rn(r, rc, q0);
 }
-// Several quotients by the SAME runtime divisor d (Acrobot divides three times by d1 per RK4 stage): the compiler's IEEE
-// fp64 division is v_div_scale x2, v_rcp_f64, two Newton steps on the reciprocal, q0 = x*r, rem = fma(-d, q0, x),
-// v_div_fmas (= fma(rem, r, q0)), v_div_fixup.  For operands that need no scaling or fix-up (normal, exponents far from
-// the limits, x != -0: true for the default-parameter dynamics) the scale factors are 1 and the fix-up is the identity,
-// so running the reciprocal part once and the 3-instruction tail per dividend reproduces `/` bit for bit
-// (tools/divcheck.hip: 0 mismatches against `/` on 4e9 random operand pairs on the MI355X).
-__device__ __forceinline__ double refined_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    double e = __fma_rn(-d, r, 1.0);
-    r = __fma_rn(r, e, r);
-    e = __fma_rn(-d, r, 1.0);
-    return __fma_rn(r, e, r);
-}
-__device__ __forceinline__ double div_with_rcp(double x, double d, double r) {
-    const double q0 = x * r;
-    return __fma_rn(__fma_rn(-d, q0, x), r, q0);
-}
+// Several quotients by the SAME runtime divisor d (Acrobot divides three times by d1 per RK4 stage): refined_rcp(d) once, then
+// div_with_rcp per dividend (mxv_divide.hpp) — the same bits as `/` for operands that need no scaling or fix-up (normal, exponents far
+// from the limits, x != -0: true for the default-parameter dynamics).
 // FINITE = the caller vouches for a finite dividend (the fused rollout on states the dynamics produced).  The Markstein sequence turns
 // an infinite dividend into a NaN (Inf * rc - c * Inf) where IEEE division keeps it infinite, and an injected state may hold one
 // (tests/golden/*_p1_nonfinite.npz: the reference's own outputs on such states): the guarded instantiations (step_kernel, rollouts after a
 // state injection) append the hardware's own special-case pass, v_div_fixup_f64 — what the compiler's `/` ends with: the quotient goes
 // through unchanged for ordinary operands, NaN / Inf / 0 operands get IEEE's answers — one instruction instead of the ten of a full division
+// (a quotient below 2^-969, where the Markstein steps run into subnormals, may still be one ulp off `/`: tests/test_gpu_device_math.py)
 // (round 4 first used `/` here: step(actions) 18.5 -> 20.1 us per 2^20-env step).
 template <int DEF, bool FINITE = true>
 __device__ __forceinline__ double div_par(double x, double c) {
@@ -301,8 +289,8 @@ __device__ __forceinline__ void sincos_kernel(double x, double *sn, double *cs) 
     // 1 - z/2 is recovered (7 instructions for the last two terms): < 0.751 ulp on |x| <= pi/4 with FMA steps, against < 0.884 ulp for the
     // two FMAs here (3e7 arguments against 80-bit cosl; 3.6 % vs 4.2 % of the values are not the correctly rounded one).  Five
     // instructions per evaluation (40 of Acrobot's 622 per env-step) for 0.13 ulp of a function whose medium-range version is bounded by
-    // its argument reduction anyway: sincos_medium's maxima, 1.466 / 1.498 ulp, are the same with either form (tools/fast_sincos_check.c
-    // -DPLAIN; timing: profiles/r4/r4g_cosine_tail_ab.txt).
+    // its argument reduction anyway: sincos_medium's maxima, 1.466 / 1.498 ulp, are the same with either form (measured on the CPU
+    // with both tails; timing: profiles/r4/r4g_cosine_tail_ab.txt).  tests/test_gpu_device_math.py holds the shipped form to these bounds.
     double c = fma_coef<F3>(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
     c = fma_coef<F3>(z, c, -2.75573143513906633035e-07);
     c = fma_coef<F3>(z, c, 2.48015872894767294178e-05);
@@ -318,10 +306,10 @@ __device__ __forceinline__ void sincos_kernel(double x, double *sn, double *cs) 
 // env-step at 82 % of the VALU issue rate, profiles/r2/r02e_rooflines.jsonl).  mx_sincos is the medium-range version the dynamics
 // need: k = rint(x * 2/pi); r = x - k*pi/2 with pi/2 split 33 + 33 + 53 bits (k * P1 and, once r is small, k * P2 are exact, so
 // cancellation near multiples of pi/2 costs no accuracy: three FMAs); the fdlibm kernel polynomials of sincos_kernel on
-// |r| <= pi/4; quadrant swap and signs from k.  Error <= 1.5 ulp over |x| <= 40 including 3e6 arguments within 5e-7 of a
-// multiple of pi/2 (ocml documents 2 ulp; checked on the CPU against 80-bit sinl/cosl with the same FMA arithmetic,
-// tools/fast_sincos_check.c), ~35 instructions.  |x| >= 2^19 (k * P1 no longer exact; never produced by these dynamics) goes to
-// ocml.  As everywhere in this file, what happens inside a libm-like helper is the library's business: the reference's own
+// |r| <= pi/4; quadrant swap and signs from k; ~35 instructions.  Error <= 1.51 ulp over |x| <= 128 (measured on the device against 80-bit
+// sinl/cosl, with the doubles next to every multiple of pi/2 among 10^7 arguments: 1.490 ulp sin, 1.507 cos; ocml documents 2 ulp),
+// growing with |x| past that as the reduction's error does (2.10 ulp below 2^12): tests/test_gpu_device_math.py.  k * P1 stays exact
+// below 2^19; mx_sincos<true> sends |x| >= 2^8 to ocml.  As everywhere in this file, what happens inside a libm-like helper is the library's business: the reference's own
 // sin/cos are glibc's resp. NumPy's SIMD loops, which differ from each other in the last bit too.
 template <int F3 = 0>
 __device__ __forceinline__ void sincos_medium(double x, double *sn, double *cs) {
@@ -348,12 +336,22 @@ __device__ __forceinline__ void sincos_medium(double x, double *sn, double *cs) 
 // angles to [-pi, pi] and bounds the velocities, MountainCar's argument is 3 * position, a time-limited Pendulum turns at most
 // 0.4 rad per step) — no range check and none of ocml's code or registers in the kernel.  mxv_set_state and unusual reset
 // bounds break that knowledge for one launch, which then takes the guarded instantiation (see launch_step_env, SAFE).
+// GUARD = true keeps the medium path to |x| < 2^8 — every argument the dynamics produce — and hands larger ones to ocml (0.78 ulp measured
+// up to 2^1000): on |x| < 2^12 the medium path measured 2.06 / 2.10 ulp (sin / cos) on the device, above ocml's 2 ulp, and up to 2^19,
+// where k * P1 is still exact, the reduction's error grows further (the previous threshold, 2^19).  It also gives sin(+-0) = +-0 as ocml and libm do: the kernel
+// polynomial and the reduction both turn -0 into +0 (fma(x*z, r, x) with x = -0 and r < 0; fma(-k, P1, x) with k = -0).  An injected
+// state holds such zeros (Pendulum at theta = -0 and theta_dot = -0 keeps them in its observation and state).  The unguarded form serves
+// states the dynamics produced and keeps neither check.
 template <bool GUARD = true, int F3 = 0>
 __device__ __forceinline__ void mx_sincos(double x, double *sn, double *cs) {
-    if (!GUARD || fabs(x) < 524288.0)
+    if constexpr (!GUARD) {
         sincos_medium<F3>(x, sn, cs);
-    else
+    } else if (fabs(x) < 256.0) {
+        sincos_medium<F3>(x, sn, cs);
+        if (x == 0.0) *sn = x;
+    } else {
         sincos(x, sn, cs);
+    }
 }
 template <bool GUARD = true, int F3 = 0>
 __device__ __forceinline__ double mx_cos(double x) {
@@ -371,6 +369,7 @@ __device__ __forceinline__ double mx_sin(double x) {
 __device__ __forceinline__ void sincos_small_or_general(double x, double *sn, double *cs) {
     if (fabs(x) <= 0.78539816339744830962) {
         sincos_kernel(x, sn, cs);
+        if (x == 0.0) *sn = x;  // sin(-0) = -0 (see mx_sincos); only injected states and non-default parameters come this way
     } else {
         mx_sincos(x, sn, cs);
     }

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/mxv.h"
+#include "mxv_divide.hpp"
 
 namespace {
 
@@ -82,37 +83,16 @@ __device__ __forceinline__ void store_row(double *base, int64_t row, const doubl
     }
 }
 
-// Three quotients by the SAME divisor per update (delta / tot, square(delta) * count / tot, M2 / tot).  The compiler's IEEE fp64 `/` is
-// v_div_scale x2, v_rcp_f64, two Newton steps, q0 = x * r, rem = fma(-d, q0, x), v_div_fmas, v_div_fixup; for operands that need no
-// scaling (exponents far from the limits) the scale factors are 1, so the reciprocal part can run once per update and each dividend pays
-// the three-instruction tail plus v_div_fixup (IEEE's answers for 0 / Inf / NaN operands) — the same bits as `/` (the form mxv_device.hpp
-// uses for Acrobot's shared divisor; tools/divcheck.hip: 0 mismatches on 4e9 operand pairs on the MI355X).  Operands outside that range
-// (a dividend outside 2^-723 .. 2^677, a divisor outside 2^-64 .. 2^64 — v_div_scale rescales when the dividend's exponent is tiny, the
-// exponents differ by 768 or more, or the quotient would be subnormal — i.e. statistics somebody injected, never the dynamics) send the
-// WAVE down the plain `/` path, so the result is IEEE division bit for bit everywhere; tests/test_gpu_subnorm.py walks both paths.
-// (v_frexp_exp_i32_f64 answers 0 for zero, Inf and NaN — v_div_fixup's business, accepted — and the true exponent for subnormals: one
-// instruction, an add and an unsigned compare per test.)
-__device__ __forceinline__ bool plain_operand(double x) {   // finite non-zero needs 2^-723 <= |x| < 2^678
-    return (uint32_t)(__builtin_amdgcn_frexp_exp(x) + 722) < 1401u;
-}
-// delta = row - mean: with |delta| in 2^-300 .. 2^300 (or 0 / Inf / NaN) and count in 2^-64 .. 2^64 (or 0), square(delta) * count lies in
-// 2^-664 .. 2^664 (or is 0 / Inf / NaN): plain by construction, no test of its own.
-__device__ __forceinline__ bool plain_delta(double x) { return (uint32_t)(__builtin_amdgcn_frexp_exp(x) + 299) < 601u; }
-__device__ __forceinline__ bool plain_divisor(double d) {   // count + 1: 1.0001 .. 2^53 in any real run
-    const uint32_t e = ((uint32_t)__double2hiint(d) >> 20) & 0x7ffu;
-    return e - 959u < 129u;
-}
-__device__ __forceinline__ double refined_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    double e = __fma_rn(-d, r, 1.0);
-    r = __fma_rn(r, e, r);
-    e = __fma_rn(-d, r, 1.0);
-    return __fma_rn(r, e, r);
-}
-__device__ __forceinline__ double div_shared(double x, double d, double r) {
-    const double q0 = x * r;
-    return __builtin_amdgcn_div_fixup(__fma_rn(__fma_rn(-d, q0, x), r, q0), d, x);
-}
+// Three quotients by the SAME divisor per update (delta / tot, square(delta) * count / tot, M2 / tot): the reciprocal part of `/` runs once
+// per update and each dividend pays the three-instruction tail plus v_div_fixup (mxv_divide.hpp: div_shared, the form mxv_device.hpp uses
+// for Acrobot's shared divisor).  Operands outside the guards' range (statistics somebody injected, never the dynamics) send the WAVE down
+// the plain `/` path, so the result is IEEE division bit for bit everywhere; tests/test_gpu_subnorm.py walks both paths and
+// tests/test_gpu_device_math.py holds div_shared to `/` wherever the guards pass, on both sides of every guard edge.
+using mxv::div_shared;
+using mxv::plain_delta;
+using mxv::plain_divisor;
+using mxv::plain_operand;
+using mxv::refined_rcp;
 
 // RunningMeanStd.update with a batch of one row (normalize.py:17-22 -> :32-47): batch_mean = x, batch_var = 0, batch_count = 1.
 template <int D>

@@ -312,6 +312,33 @@ def run_p1_nonfinite(engine_cls, name, strict):
     return int(np.isnan(g["state1"]).any(axis=1).sum())
 
 
+def same_bits(a, b):
+    """Element-wise bit equality of two float arrays of one dtype: unlike ulps32 and `==`, -0.0 and +0.0 differ."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
+    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    return a.view(u) == b.view(u)
+
+
+def run_p1_signed_zero(engine_cls, name, rows=None):
+    """<env>_p1_signed_zero.npz (tests/golden/make_golden_signed_zero.py): one step from states and actions made of +-0 components.
+    Observations, rewards and post-step states must equal the reference's bit for bit, signs of zero included, on `rows` (all by default);
+    returns the golden and the engine's (obs, reward, state) for the caller's own checks of the other rows."""
+    g = load_golden(name, "p1_signed_zero")
+    n = len(g["action"])
+    eng = engine_cls(name, n, 0, autoreset=False)
+    elapsed = np.where(g["fresh"] == 1, 0, 5).astype(np.int32)
+    eng.set_state(g["state0"].T, elapsed)
+    obs, rew, term, trunc, fin = eng.step(g["action"])
+    st = np.ascontiguousarray(eng.get_state()[0].T)
+    assert np.array_equal(term, g["terminated"].astype(bool)) and not trunc.any(), f"{name}: masks differ on signed-zero inputs"
+    rows = np.ones(n, bool) if rows is None else rows
+    for what, got, ref in (("obs", obs, g["obs"]), ("reward", rew, g["reward"]), ("state", st, g["state1"])):
+        ok = same_bits(got, ref).reshape(n, -1).all(axis=1) | ~rows
+        assert ok.all(), f"{name}: {what} differs in rows {np.flatnonzero(~ok)[:8]}: {got[~ok][:2]} vs {ref[~ok][:2]}"
+    return g, (obs, rew, st)
+
+
 def run_cartpole_beyond(engine_cls, strict):
     """CartPole_p2_beyond.npz (tests/golden/make_golden_cartpole_beyond.py): envs stepped on after they terminated, no reset in between
     (MXV_FLAG_NO_AUTORESET): the fall pays 1.0, every later terminated step 0.0 (cartpole.py:169-184)."""
@@ -695,3 +722,20 @@ def toytext_stats_start(g, mdp=None):
         return g["first"].astype(np.int8)
     u = g["first"][:, 0]
     return np.array([int(np.argmax(mdp.initial_cum > x)) for x in u], dtype=np.int32)
+
+
+# ---- tests/device_math/primitives.hip: the device math helpers as shipped, one kernel per helper ----------------------------------
+DEVICE_MATH_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "device_math", "primitives.hip")
+# the library's own flags (gym_amd/csrc/build.sh)
+DEVICE_MATH_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-result"]
+
+
+def build_device_math(out_dir):
+    """Compile primitives.hip into out_dir/libprimitives.so with the library's flags; returns the path."""
+    import subprocess
+
+    lib = os.path.join(str(out_dir), "libprimitives.so")
+    p = subprocess.run(["/opt/rocm/bin/hipcc", *DEVICE_MATH_FLAGS, "-shared", DEVICE_MATH_SRC, "-o", lib], capture_output=True, text=True,
+                       timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return lib

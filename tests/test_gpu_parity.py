@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import (DISCRETE, ENV_IDS, ENV_NAMES, GYM_IDS, LIMITS, MAX_OBS_ULPS, OBS_RTOL, REWARD_ATOL, REWARD_ATOL_DEFAULT, REWARD_RTOL,
-                     HipEngine, OracleEngine, run_cartpole_beyond, run_p1, run_p1_nonfinite, run_p2, ulps32)
+                     HipEngine, OracleEngine, STATE_ATOL, STATE_RTOL, run_cartpole_beyond, run_p1, run_p1_nonfinite, run_p1_signed_zero, run_p2, ulps32)
 
 pytestmark = pytest.mark.gpu
 
@@ -129,6 +129,29 @@ def test_non_finite_inputs_pass_through_like_the_reference(name):
     """A NaN Box action (a diverged policy) or state component comes out of the reference as NaN observations / rewards — np.clip and
     Python's comparisons propagate it — and must not be turned into a bound by the device's v_max / v_min clamps."""
     assert run_p1_nonfinite(HipEngine, name, strict=False) > 100
+
+
+@pytest.mark.parametrize("name", ["CartPole", "Pendulum", "MountainCar", "MountainCarContinuous"])
+def test_signed_zero_inputs_bit_exact(name):
+    """make_golden_signed_zero.py: set_state + step from +-0 states and actions; every output equals the reference's bit for bit, the
+    sign of each zero included (Pendulum at theta = theta_dot = u = -0 keeps obs [1, -0, -0] and state (-0, -0))."""
+    run_p1_signed_zero(HipEngine, name)
+
+
+def test_signed_zero_inputs_acrobot():
+    """Acrobot from +-0 states: with torque +-1 the outputs are the reference's to the engine's usual bars.  With torque 0 the reference
+    leaves residues of ~1e-17 (it takes cos(fl(theta1 + theta2) - fl(pi / 2)), and cos(-fl(pi / 2)) = 6.1e-17) where the engine's angle
+    identities give exact zeros (mxv_device.hpp, Acrobot's trig budget): held to 1e-15 absolute there."""
+    from helpers import load_golden
+
+    torque0 = load_golden("Acrobot", "p1_signed_zero")["action"] == 1
+    g, (obs, rew, st) = run_p1_signed_zero(HipEngine, "Acrobot", rows=np.zeros(torque0.size, bool))
+    assert np.array_equal(rew, g["reward"])
+    m = ~torque0
+    assert ulps32(obs[m], g["obs"][m]).max() <= MAX_OBS_ULPS
+    np.testing.assert_allclose(st[m], g["state1"][m], rtol=STATE_RTOL, atol=STATE_ATOL)
+    np.testing.assert_allclose(st[torque0], g["state1"][torque0], rtol=0, atol=1e-15)
+    np.testing.assert_allclose(obs[torque0], g["obs"][torque0], rtol=0, atol=1e-15)
 
 
 @pytest.mark.parametrize("name", ["Pendulum", "MountainCarContinuous"])

@@ -306,3 +306,16 @@ def test_kernel_sources_test_no_ab_switches():
                     if m:
                         tested |= set(re.findall(r"\bMXV_\w+", m.group(1).split("//")[0]))
     assert tested == {"MXV_PENDULUM_GLIBC_POWF", "MXV_XFN", "MXV_XCONST", "MXV_XCOLD"}, sorted(tested)
+
+
+def test_device_math_harness_cross_compiles(tmp_path):
+    """tests/device_math/primitives.hip (the harness of tests/test_gpu_device_math.py) includes mxv_device.hpp and mxv_divide.hpp as
+    they ship: a header change that breaks a helper's signature or an instantiation the engine uses fails here, without a GPU."""
+    from helpers import build_device_math
+
+    lib = build_device_math(tmp_path)
+    syms = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    for name in ("sincos_kernel_f0", "sincos_medium_f3", "mx_sincos_guarded_pendulum", "mx_sincos_fast_acrobot", "sincos_small_or_general_op",
+                 "div_par_finite", "div_par_fixup", "div_with_rcp_op", "div_shared_op", "plain_guards", "fmod_const_2pi", "np_remainder_2pi",
+                 "np_remainder_bounded_2pi", "clamp_range_f64", "clamp_range_hi_first_f32", "nan_through_op", "glibc_powf_square_op"):
+        assert re.search(rf" T {name}$", syms, re.M), name
