@@ -185,8 +185,6 @@ def _load():
         "mxv_default_reset_bounds": ([i32, vp], C.c_int),
         "mxv_version": ([], C.c_char_p),
         "mxv_create": ([C.POINTER(MxvConfig), C.POINTER(vp)], C.c_int),
-        "mxv_destroy": ([vp], C.c_int),
-        "mxv_last_error": ([vp], C.c_char_p),
         "mxv_seed": ([vp, u64, vp], C.c_int),
         "mxv_seed_actions": ([vp, u64], C.c_int),
         "mxv_reset": ([vp, vp, vp, vp], C.c_int),
@@ -201,9 +199,7 @@ def _load():
         "mxv_get_state": ([vp, vp, vp], C.c_int),
         "mxv_adopt_obs": ([vp, vp], C.c_int),
         "mxv_set_state": ([vp, vp, vp], C.c_int),
-        "mxv_get_counters": ([vp, C.POINTER(u64), C.POINTER(u32)], C.c_int),
         "mxv_set_counters": ([vp, u64, u32], C.c_int),
-        "mxv_set_device_clock": ([vp, i32], C.c_int),
         "mxv_set_obs_partials": ([vp, vp], C.c_int),
         "mxv_set_return_partials": ([vp, vp, C.c_double, vp], C.c_int),
         "mxv_obs_partials_layout": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)], C.c_int),
@@ -234,20 +230,11 @@ def _load():
         "mxv_set_params": ([vp, vp], C.c_int),
         "mxv_set_params_per_env": ([vp, vp], C.c_int),
         "mxv_get_params_per_env": ([vp, vp], C.c_int),
-        "mxv_episode_stats": ([vp, i32], C.c_int),
-        "mxv_set_episode_outputs": ([vp, vp, vp], C.c_int),
-        "mxv_episode_stats_host": ([vp, vp, vp, vp], C.c_int),
-        "mxv_set_running_returns": ([vp, vp], C.c_int),
-        "mxv_sync": ([vp], C.c_int),
         "mxv_get_stream": ([vp, C.POINTER(vp)], C.c_int),
-        "mxv_set_stream": ([vp, vp], C.c_int),
         "mxv_host_io": ([vp] + [C.POINTER(vp)] * 6, C.c_int),
         "mxv_step_mapped": ([vp], C.c_int),
         "mxv_reset_mapped": ([vp, vp], C.c_int),
         "mxv_norm_create": ([i32, i32, i64, vp, C.POINTER(vp)], C.c_int),
-        "mxv_norm_destroy": ([vp], C.c_int),
-        "mxv_norm_last_error": ([vp], C.c_char_p),
-        "mxv_norm_set_stream": ([vp, vp], C.c_int),
         "mxv_norm_get_state": ([vp, vp, vp, vp, vp], C.c_int),
         "mxv_norm_set_state": ([vp, vp, vp, C.c_double, vp], C.c_int),
         "mxv_norm_observations": ([vp, i32, vp, vp, i32, C.c_double], C.c_int),
@@ -260,16 +247,11 @@ def _load():
         "mxv_norm_reward_sums": ([vp, i32, vp, i32, vp, vp, C.c_double, vp], C.c_int),
         "mxv_norm_reward_apply": ([vp, i32, vp, i32, vp, C.c_double, vp, i32, i64], C.c_int),
         "mxv_subnorm_create": ([i32, i32, i64, vp, C.POINTER(vp)], C.c_int),
-        "mxv_subnorm_destroy": ([vp], C.c_int),
-        "mxv_subnorm_last_error": ([vp], C.c_char_p),
-        "mxv_subnorm_set_stream": ([vp, vp], C.c_int),
         "mxv_subnorm_get_state": ([vp, vp, vp, vp, vp], C.c_int),
         "mxv_subnorm_set_state": ([vp, vp, vp, vp, vp], C.c_int),
         "mxv_subnorm_observations": ([vp, i32, vp, vp, vp, vp, vp, i32, vp, C.c_double], C.c_int),
         "mxv_subnorm_rewards": ([vp, i32, vp, i32, vp, vp, vp, C.c_double, C.c_double], C.c_int),
         "mxv_tab_create": ([C.POINTER(MxvTabConfig), vp, vp, vp, vp, vp, vp, C.POINTER(vp)], C.c_int),
-        "mxv_tab_destroy": ([vp], C.c_int),
-        "mxv_tab_last_error": ([vp], C.c_char_p),
         "mxv_tab_seed": ([vp, u64, vp], C.c_int),
         "mxv_tab_seed_actions": ([vp, u64], C.c_int),
         "mxv_tab_reset": ([vp, vp, vp], C.c_int),
@@ -279,26 +261,11 @@ def _load():
         "mxv_tab_reset_host": ([vp, vp, vp], C.c_int),
         "mxv_tab_step_host": ([vp] * 10, C.c_int),
         "mxv_tab_get_state": ([vp, vp, vp], C.c_int),
-        "mxv_tab_episode_stats": ([vp, i32], C.c_int),
-        "mxv_tab_set_episode_outputs": ([vp, vp, vp], C.c_int),
-        "mxv_tab_episode_stats_host": ([vp, vp, vp, vp], C.c_int),
-        "mxv_bj_episode_stats": ([vp, i32], C.c_int),
-        "mxv_bj_set_episode_outputs": ([vp, vp, vp], C.c_int),
-        "mxv_bj_episode_stats_host": ([vp, vp, vp, vp], C.c_int),
-        "mxv_tab_set_running_returns": ([vp, vp], C.c_int),
-        "mxv_bj_set_running_returns": ([vp, vp], C.c_int),
         "mxv_tab_set_state": ([vp, vp, vp], C.c_int),
-        "mxv_tab_get_counters": ([vp, C.POINTER(u64), C.POINTER(u32)], C.c_int),
         "mxv_tab_set_counters": ([vp, u64, u32], C.c_int),
-        "mxv_tab_sync": ([vp], C.c_int),
         "mxv_tab_last_kernel": ([vp], C.c_int),
-        "mxv_tab_set_device_clock": ([vp, i32], C.c_int),
-        "mxv_bj_set_device_clock": ([vp, i32], C.c_int),
         "mxv_tab_word_threshold": ([C.c_double], u64),
-        "mxv_tab_set_stream": ([vp, vp], C.c_int),
         "mxv_bj_create": ([C.POINTER(MxvBjConfig), C.POINTER(vp)], C.c_int),
-        "mxv_bj_destroy": ([vp], C.c_int),
-        "mxv_bj_last_error": ([vp], C.c_char_p),
         "mxv_bj_seed": ([vp, u64, vp, u64], C.c_int),
         "mxv_bj_reset": ([vp, vp, vp, vp], C.c_int),
         "mxv_bj_step": ([vp] * 8, C.c_int),
@@ -308,15 +275,19 @@ def _load():
         "mxv_bj_step_host": ([vp] * 8, C.c_int),
         "mxv_bj_get_state": ([vp, vp, vp], C.c_int),
         "mxv_bj_set_state": ([vp, vp, vp, u64, u32], C.c_int),
-        "mxv_bj_get_counters": ([vp, vp, vp], C.c_int),
-        "mxv_bj_sync": ([vp], C.c_int),
-        "mxv_bj_set_stream": ([vp, vp], C.c_int),
         "mxv_placed_alloc": ([i32, i32, vp, vp, i32, vp, C.POINTER(vp)], C.c_int),
         "mxv_placed_free": ([vp], C.c_int),
         "mxv_hbm_pair_probe": ([i32, vp, vp, i32, C.POINTER(C.c_double)], C.c_int),
         "mxv_placed_info_get": ([vp, C.POINTER(MxvPlacedInfo)], C.c_int),
         "mxv_placed_last_error": ([vp], C.c_char_p),
     }
+    for p in ("mxv", "mxv_norm", "mxv_subnorm", "mxv_tab", "mxv_bj"):   # what every object has (_Object)
+        sig.update({f"{p}_destroy": ([vp], C.c_int), f"{p}_last_error": ([vp], C.c_char_p), f"{p}_set_stream": ([vp, vp], C.c_int)})
+    for p in ("mxv", "mxv_tab", "mxv_bj"):                             # what every engine handle has (_Engine)
+        sig.update({f"{p}_episode_stats": ([vp, i32], C.c_int), f"{p}_set_episode_outputs": ([vp, vp, vp], C.c_int),
+                    f"{p}_episode_stats_host": ([vp, vp, vp, vp], C.c_int), f"{p}_set_running_returns": ([vp, vp], C.c_int),
+                    f"{p}_get_counters": ([vp, C.POINTER(u64), C.POINTER(u32)], C.c_int), f"{p}_set_device_clock": ([vp, i32], C.c_int),
+                    f"{p}_sync": ([vp], C.c_int)})
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the .so does not export a declared symbol
         fn.argtypes = argtypes
@@ -471,8 +442,111 @@ class _DestroyLater:
             pass
 
 
-class Handle:
+def _u64(x) -> int:
+    return int(x) & (2**64 - 1)
+
+
+class _Object:
+    """What every library object shares: its pointer `_h`, the error report, teardown and the stream.  `_prefix` names the object's C
+    functions (<prefix>_create, _destroy, _last_error, _set_stream, ...)."""
+
+    _prefix = ""
+
+    def _fn(self, name: str):
+        return getattr(lib, f"{self._prefix}_{name}")
+
+    def _adopt(self, rc: int, h):
+        """Keep what <prefix>_create made, or raise with the create error."""
+        if rc != OK:
+            raise MxvError(rc, (self._fn("last_error")(None) or b"").decode())
+        self._h = h
+
+    def _check(self, rc: int):
+        if rc != OK:
+            raise MxvError(rc, (self._fn("last_error")(self._h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        self._check(self._fn("set_stream")(self._h, C.c_void_p(stream_ptr or None)))
+
+
+class _Engine(_Object):
+    """What the engine handles (Handle, Tab, Blackjack) share: seed bookkeeping, fused episode statistics, the step counters and the
+    device clock, the common part of snapshot()."""
+
+    def _init_seeds(self, seed: int, action_seed: int):
+        self._base_seed, self._per_env_seeds = _u64(seed), None
+        self._action_seed = _u64(action_seed)
+        self._stats_on = False
+
+    def _seed(self, base_seed: int, per_env_seeds, *more):
+        if per_env_seeds is not None:
+            per_env_seeds = np.ascontiguousarray(per_env_seeds, dtype=np.uint64).copy()
+            assert per_env_seeds.shape == (self.num_envs,)
+        self._check(self._fn("seed")(self._h, _u64(base_seed), _ptr(per_env_seeds), *more))
+        self._base_seed, self._per_env_seeds = _u64(base_seed), per_env_seeds
+
+    def seed(self, base_seed: int, per_env_seeds=None):
+        self._seed(base_seed, per_env_seeds)
+
+    def get_counters(self):
+        t, r = C.c_uint64(), C.c_uint32()
+        self._check(self._fn("get_counters")(self._h, C.byref(t), C.byref(r)))
+        return t.value, r.value
+
+    def set_device_clock(self, on: bool = True):
+        """The step index lives in device memory and advances on the stream (mxv_set_device_clock): calls of this handle can then be
+        recorded into a caller's hipGraph and replayed."""
+        self._check(self._fn("set_device_clock")(self._h, 1 if on else 0))
+
+    def sync(self):
+        self._check(self._fn("sync")(self._h))
+
+    # -- episode statistics (gym.wrappers.RecordEpisodeStatistics fused into the kernels) ------------------------------------------------
+    def episode_stats(self, enable: bool = True):
+        self._check(self._fn("episode_stats")(self._h, 1 if enable else 0))
+        self._stats_on = bool(enable)
+
+    def set_episode_outputs(self, ep_return_dev=None, ep_length_dev=None):
+        """[N] / [K][N] device arrays (float32 returns, int32 lengths) the device-pointer calls fill where an episode ended; None detaches."""
+        self._check(self._fn("set_episode_outputs")(self._h, _ptr(ep_return_dev), _ptr(ep_length_dev)))
+
+    def episode_stats_host(self, want_running: bool = False):
+        """(returns, lengths[, running_returns]) of the last step_host call; valid where terminated | truncated."""
+        r = np.zeros(self.num_envs, dtype=np.float32)
+        l = np.zeros(self.num_envs, dtype=np.int32)
+        run = np.zeros(self.num_envs, dtype=np.float32) if want_running else None
+        self._check(self._fn("episode_stats_host")(self._h, r.ctypes.data, l.ctypes.data, _ptr(run)))
+        return (r, l, run) if want_running else (r, l)
+
+    def set_running_returns(self, running):
+        r = np.ascontiguousarray(running, dtype=np.float32).reshape(self.num_envs)
+        self._check(self._fn("set_running_returns")(self._h, r.ctypes.data))
+
+    def snapshot(self) -> dict:
+        """State + TimeLimit counters + RNG seeds and counters + running episode returns (plain NumPy / ints: picklable)."""
+        state, elapsed = self.get_state()
+        t, r = self.get_counters()
+        return dict(num_envs=self.num_envs, state=state, elapsed=elapsed, t=t, r=r, base_seed=self._base_seed,
+                    per_env_seeds=None if self._per_env_seeds is None else self._per_env_seeds.copy(),
+                    action_seed=self._action_seed, stats_on=self._stats_on,
+                    running_returns=self.episode_stats_host(want_running=True)[2] if self._stats_on else None)
+
+
+class Handle(_Engine):
     """One engine handle = one device + one stream + N device-resident envs (see include/mxv.h)."""
+
+    _prefix = "mxv"
 
     def __init__(self, env_id: int, num_envs: int, max_episode_steps: int, *, device: int = 0, env_offset: int = 0,
                  seed: int = 0, action_seed: int = 0, flags: int = 0):
@@ -483,23 +557,14 @@ class Handle:
         self.device = int(device)
         self.env_offset = int(env_offset)
         cfg = MxvConfig(self.env_id, self.device, self.num_envs, self.env_offset, int(max_episode_steps), self.flags,
-                        int(seed) & (2**64 - 1), int(action_seed) & (2**64 - 1))
+                        _u64(seed), _u64(action_seed))
         h = C.c_void_p()
-        rc = lib.mxv_create(C.byref(cfg), C.byref(h))
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_last_error(None) or b"").decode())
-        self._h = h
+        self._adopt(lib.mxv_create(C.byref(cfg), C.byref(h)), h)
         self.max_episode_steps = int(max_episode_steps)
-        self._base_seed, self._per_env_seeds = int(seed) & (2**64 - 1), None
-        self._action_seed = int(action_seed) & (2**64 - 1)
-        self._stats_on = False
+        self._init_seeds(seed, action_seed)
         self._per_env_params = False
 
     # -- plumbing -------------------------------------------------------------------------
-    def _check(self, rc: int):
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_last_error(self._h) or b"").decode())
-
     @property
     def action_dtype(self):
         if self.NA > 0:
@@ -511,34 +576,15 @@ class Handle:
         return np.float32 if self.flags & FLAG_REWARD_F32 else np.float64
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            keep = getattr(self, "_io_keep", None)
-            if keep is not None:
-                self._io_keep = None   # mapped-I/O views may outlive close(): the last one to die destroys the handle
-            else:
-                lib.mxv_destroy(self._h)
+        if getattr(self, "_io_keep", None) is not None:
+            self._io_keep = None   # mapped-I/O views may outlive close(): the last one to die destroys the handle
             self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     # -- ABI calls ------------------------------------------------------------------------
-    def seed(self, base_seed: int, per_env_seeds=None):
-        p = None
-        if per_env_seeds is not None:
-            per_env_seeds = np.ascontiguousarray(per_env_seeds, dtype=np.uint64)
-            assert per_env_seeds.shape == (self.num_envs,)
-            p = per_env_seeds.ctypes.data
-        self._check(lib.mxv_seed(self._h, int(base_seed) & (2**64 - 1), p))
-        self._base_seed = int(base_seed) & (2**64 - 1)
-        self._per_env_seeds = None if per_env_seeds is None else per_env_seeds.copy()
-
     def seed_actions(self, action_seed: int):
-        self._check(lib.mxv_seed_actions(self._h, int(action_seed) & (2**64 - 1)))
-        self._action_seed = int(action_seed) & (2**64 - 1)
+        self._check(lib.mxv_seed_actions(self._h, _u64(action_seed)))
+        self._action_seed = _u64(action_seed)
 
     @staticmethod
     def _bounds(bounds):
@@ -730,11 +776,6 @@ class Handle:
         self._check(lib.mxv_last_launch(self._h, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in MxvLaunchInfo._fields_}
 
-    def get_counters(self):
-        t, r = C.c_uint64(), C.c_uint32()
-        self._check(lib.mxv_get_counters(self._h, C.byref(t), C.byref(r)))
-        return t.value, r.value
-
     def set_counters(self, t: int, r: int):
         self._check(lib.mxv_set_counters(self._h, int(t), int(r)))
 
@@ -753,11 +794,6 @@ class Handle:
         lv, per, vals = C.c_int64(), C.c_int64(), C.c_int32()
         self._check(lib.mxv_obs_partials_layout(self._h, C.byref(lv), C.byref(per), C.byref(vals)))
         return lv.value, per.value, vals.value
-
-    def set_device_clock(self, on: bool = True):
-        """The step index lives in device memory and advances on the stream (mxv_set_device_clock): calls of this handle can then be
-        recorded into a caller's hipGraph and replayed."""
-        self._check(lib.mxv_set_device_clock(self._h, 1 if on else 0))
 
     def get_episodes(self) -> np.ndarray:
         """Per-env reset ordinals (uint32 [N]): how many resets each env has had since seeding = the position of its reset
@@ -799,10 +835,6 @@ class Handle:
         single steps that pass it as their obs — it must not be written in between and must outlive the adoption."""
         self._check(lib.mxv_adopt_obs(self._h, _ptr(obs_dev)))
 
-    def episode_stats(self, enable: bool = True):
-        self._check(lib.mxv_episode_stats(self._h, 1 if enable else 0))
-        self._stats_on = bool(enable)
-
     def set_running_returns(self, running):
         r = np.ascontiguousarray(running, dtype=np.float32)
         assert r.shape == (self.num_envs,)
@@ -812,17 +844,10 @@ class Handle:
     def snapshot(self) -> dict:
         """Everything a fresh handle needs to continue this one bit-identically (plain NumPy / ints: picklable): env state,
         TimeLimit counters, RNG seeds and counters, physics parameters, running episode returns."""
-        state, elapsed = self.get_state()
-        t, r = self.get_counters()
-        snap = dict(format=SNAPSHOT_FORMAT, env_id=self.env_id, num_envs=self.num_envs, max_episode_steps=self.max_episode_steps,
-                    env_offset=self.env_offset, flags=self.flags, base_seed=self._base_seed,
-                    per_env_seeds=None if self._per_env_seeds is None else self._per_env_seeds.copy(),
-                    action_seed=self._action_seed, state=state, elapsed=elapsed, t=t, r=r, episodes=self.get_episodes(),
+        return dict(super().snapshot(), format=SNAPSHOT_FORMAT, env_id=self.env_id, max_episode_steps=self.max_episode_steps,
+                    env_offset=self.env_offset, flags=self.flags, episodes=self.get_episodes(),
                     params=self.get_params_per_env() if self._per_env_params else self.get_params(),
-                    per_env_params=self._per_env_params, stats_on=self._stats_on, running_returns=None, beyond=self.get_beyond())
-        if self._stats_on:
-            snap["running_returns"] = self.episode_stats_host(want_running=True)[2]
-        return snap
+                    per_env_params=self._per_env_params, beyond=self.get_beyond())
 
     def restore(self, snap: dict):
         # format 2 (round 2): reset draws are indexed by per-env reset ordinals (`episodes`).  Older snapshots carry no ordinals and
@@ -863,20 +888,6 @@ class Handle:
         b = np.ascontiguousarray(beyond, dtype=np.uint8).reshape(self.num_envs)
         self._check(lib.mxv_set_beyond(self._h, b.ctypes.data))
 
-    def set_episode_outputs(self, ep_return_dev=None, ep_length_dev=None):
-        self._check(lib.mxv_set_episode_outputs(self._h, _ptr(ep_return_dev), _ptr(ep_length_dev)))
-
-    def episode_stats_host(self, want_running: bool = False):
-        """(returns, lengths[, running_returns]) of the last step_host call; valid where terminated | truncated."""
-        r = np.zeros(self.num_envs, dtype=np.float32)
-        l = np.zeros(self.num_envs, dtype=np.int32)
-        run = np.zeros(self.num_envs, dtype=np.float32) if want_running else None
-        self._check(lib.mxv_episode_stats_host(self._h, r.ctypes.data, l.ctypes.data, _ptr(run)))
-        return (r, l, run) if want_running else (r, l)
-
-    def sync(self):
-        self._check(lib.mxv_sync(self._h))
-
     def wait_stream(self, stream_ptr: int):
         """mxv_wait_stream: the handle's stream waits (on the GPU) for everything queued on hipStream_t `stream_ptr` so far."""
         self._check(lib.mxv_wait_stream(self._h, C.c_void_p(stream_ptr)))
@@ -886,9 +897,6 @@ class Handle:
         s = C.c_void_p()
         self._check(lib.mxv_get_stream(self._h, C.byref(s)))
         return s.value or 0
-
-    def set_stream(self, stream_ptr: int):
-        self._check(lib.mxv_set_stream(self._h, C.c_void_p(stream_ptr)))
 
     def set_final_snapshot(self, obs=None, reward=None, terminated=None, truncated=None):
         """Every following K-step rollout also writes its last step's outputs into these device buffers (None: detach)."""
@@ -1050,34 +1058,15 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-class Norm:
+class Norm(_Object):
     """One mxv_norm = one device-resident RunningMeanStd (+ NormalizeReward's return accumulators); see include/mxv.h."""
+
+    _prefix = "mxv_norm"
 
     def __init__(self, dim: int, num_envs: int, *, device: int = 0, stream: int = 0):
         self.dim, self.num_envs, self.device = int(dim), int(num_envs), int(device)
         h = C.c_void_p()
-        rc = lib.mxv_norm_create(self.device, self.dim, self.num_envs, C.c_void_p(stream or None), C.byref(h))
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_norm_last_error(None) or b"").decode())
-        self._h = h
-
-    def _check(self, rc: int):
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_norm_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.mxv_norm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: int):
-        self._check(lib.mxv_norm_set_stream(self._h, C.c_void_p(stream_ptr or None)))
+        self._adopt(lib.mxv_norm_create(self.device, self.dim, self.num_envs, C.c_void_p(stream or None), C.byref(h)), h)
 
     def get_state(self, want_returns: bool = False):
         """(mean[dim], var[dim], count[, returns[num_envs]]) as float64 host values."""
@@ -1130,36 +1119,17 @@ class Norm:
                                               float(epsilon), _ptr(all_sums_dev), int(world), int(total_rows)))
 
 
-class SubNorm:
+class SubNorm(_Object):
     """One mxv_subnorm = num_envs device-resident RunningMeanStd objects of shape (dim,), each fed with batches of one row (+ every
     sub-env's discounted return): the per-sub-env NormalizeObservation / NormalizeReward of `make(wrappers=[...])`; see
     include/mxv_norm.h."""
 
+    _prefix = "mxv_subnorm"
+
     def __init__(self, dim: int, num_envs: int, *, device: int = 0, stream: int = 0):
         self.dim, self.num_envs, self.device = int(dim), int(num_envs), int(device)
         h = C.c_void_p()
-        rc = lib.mxv_subnorm_create(self.device, self.dim, self.num_envs, C.c_void_p(stream or None), C.byref(h))
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_subnorm_last_error(None) or b"").decode())
-        self._h = h
-
-    def _check(self, rc: int):
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_subnorm_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.mxv_subnorm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: int):
-        self._check(lib.mxv_subnorm_set_stream(self._h, C.c_void_p(stream_ptr or None)))
+        self._adopt(lib.mxv_subnorm_create(self.device, self.dim, self.num_envs, C.c_void_p(stream or None), C.byref(h)), h)
 
     def get_state(self):
         """(mean[num_envs][dim], var[num_envs][dim], count[num_envs], returns[num_envs]) as float64 host arrays."""
@@ -1188,8 +1158,10 @@ class SubNorm:
         return out_dev
 
 
-class Tab:
+class Tab(_Engine):
     """One mxv_tab handle = one device + one stream + N device-resident copies of a tabular MDP (see include/mxv.h)."""
+
+    _prefix = "mxv_tab"
 
     def __init__(self, num_states, num_actions, cum_prob, prob, next_state, reward, terminated, initial_cum, num_envs,
                  max_episode_steps, *, device=0, env_offset=0, seed=0, action_seed=0, compact=False, general_kernel=False):
@@ -1209,54 +1181,15 @@ class Tab:
         self.S, self.A, self.M, self.num_envs, self.device = S, A, M, int(num_envs), int(device)
         cfg = MxvTabConfig(self.device, S, A, M, self.num_envs, int(env_offset), int(max_episode_steps),
                            (TAB_FLAG_COMPACT if compact else 0) | (TAB_FLAG_GENERAL_KERNEL if general_kernel else 0),
-                           int(seed) & (2**64 - 1), int(action_seed) & (2**64 - 1))
+                           _u64(seed), _u64(action_seed))
         h = C.c_void_p()
-        rc = lib.mxv_tab_create(C.byref(cfg), cum.ctypes.data, pr.ctypes.data, nx.ctypes.data, rw.ctypes.data,
-                                te.ctypes.data, ic.ctypes.data, C.byref(h))
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_tab_last_error(None) or b"").decode())
-        self._h = h
-        self._base_seed, self._per_env_seeds = int(seed) & (2**64 - 1), None
-        self._action_seed = int(action_seed) & (2**64 - 1)
-
-    def _check(self, rc: int):
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_tab_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.mxv_tab_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def seed(self, base_seed: int, per_env_seeds=None):
-        p = None
-        if per_env_seeds is not None:
-            per_env_seeds = np.ascontiguousarray(per_env_seeds, dtype=np.uint64)
-            assert per_env_seeds.shape == (self.num_envs,)
-            p = per_env_seeds.ctypes.data
-        self._check(lib.mxv_tab_seed(self._h, int(base_seed) & (2**64 - 1), p))
-        self._base_seed = int(base_seed) & (2**64 - 1)
-        self._per_env_seeds = None if per_env_seeds is None else per_env_seeds.copy()
+        self._adopt(lib.mxv_tab_create(C.byref(cfg), cum.ctypes.data, pr.ctypes.data, nx.ctypes.data, rw.ctypes.data,
+                                       te.ctypes.data, ic.ctypes.data, C.byref(h)), h)
+        self._init_seeds(seed, action_seed)
 
     def seed_actions(self, action_seed: int):
-        self._check(lib.mxv_tab_seed_actions(self._h, int(action_seed) & (2**64 - 1)))
-        self._action_seed = int(action_seed) & (2**64 - 1)
-
-    def snapshot(self) -> dict:
-        """State + TimeLimit counters + RNG seeds and counters (the table itself belongs to the caller's MDP)."""
-        st, el = self.get_state()
-        t, r = self.get_counters()
-        on = getattr(self, "_stats_on", False)
-        return dict(num_envs=self.num_envs, state=st, elapsed=el, t=t, r=r, base_seed=self._base_seed,
-                    per_env_seeds=None if self._per_env_seeds is None else self._per_env_seeds.copy(),
-                    action_seed=self._action_seed, stats_on=on,
-                    running_returns=self.episode_stats_host(want_running=True)[2] if on else None)
+        self._check(lib.mxv_tab_seed_actions(self._h, _u64(action_seed)))
+        self._action_seed = _u64(action_seed)
 
     def restore(self, snap: dict):
         if snap["num_envs"] != self.num_envs:
@@ -1268,10 +1201,6 @@ class Tab:
         if snap.get("stats_on"):
             self.episode_stats(True)
             self.set_running_returns(snap["running_returns"])
-
-    def set_device_clock(self, on: bool = True):
-        """The step index in device memory, advanced on the stream: step / rollout calls become recordable in a caller's hipGraph."""
-        self._check(lib.mxv_tab_set_device_clock(self._h, 1 if on else 0))
 
     def last_kernel(self) -> int:
         """TAB_KERNEL_GENERAL / TAB_KERNEL_TRAJECTORY: which kernel the last step / rollout call launched (mxv_tab_last_kernel)."""
@@ -1329,27 +1258,6 @@ class Tab:
                                           trunc.ctypes.data, prob.ctypes.data, fin.ctypes.data, fprob.ctypes.data))
         return obs, rew, term.view(np.bool_), trunc.view(np.bool_), prob, fin, fprob
 
-    # -- episode statistics (gym.wrappers.RecordEpisodeStatistics fused into the kernels; include/mxv_toytext.h) --------------------------
-    def episode_stats(self, enable: bool = True):
-        self._check(lib.mxv_tab_episode_stats(self._h, 1 if enable else 0))
-        self._stats_on = bool(enable)
-
-    def set_episode_outputs(self, ep_return_dev=None, ep_length_dev=None):
-        """[N] / [K][N] device arrays (float32 returns, int32 lengths) the device-pointer calls fill where an episode ended; None detaches."""
-        self._check(lib.mxv_tab_set_episode_outputs(self._h, _ptr(ep_return_dev), _ptr(ep_length_dev)))
-
-    def episode_stats_host(self, want_running: bool = False):
-        """(returns, lengths[, running_returns]) of the last step_host call; valid where terminated | truncated."""
-        r = np.zeros(self.num_envs, dtype=np.float32)
-        l = np.zeros(self.num_envs, dtype=np.int32)
-        run = np.zeros(self.num_envs, dtype=np.float32) if want_running else None
-        self._check(lib.mxv_tab_episode_stats_host(self._h, r.ctypes.data, l.ctypes.data, _ptr(run)))
-        return (r, l, run) if want_running else (r, l)
-
-    def set_running_returns(self, running):
-        r = np.ascontiguousarray(running, dtype=np.float32).reshape(self.num_envs)
-        self._check(lib.mxv_tab_set_running_returns(self._h, r.ctypes.data))
-
     def get_state(self):
         st = np.empty(self.num_envs, dtype=np.int32)
         el = np.empty(self.num_envs, dtype=np.int32)
@@ -1361,19 +1269,8 @@ class Tab:
         el = None if elapsed is None else np.ascontiguousarray(elapsed, dtype=np.int32).reshape(self.num_envs)
         self._check(lib.mxv_tab_set_state(self._h, _ptr(st), _ptr(el)))
 
-    def get_counters(self):
-        t, r = C.c_uint64(), C.c_uint32()
-        self._check(lib.mxv_tab_get_counters(self._h, C.byref(t), C.byref(r)))
-        return t.value, r.value
-
     def set_counters(self, t: int, r: int):
         self._check(lib.mxv_tab_set_counters(self._h, int(t), int(r)))
-
-    def sync(self):
-        self._check(lib.mxv_tab_sync(self._h))
-
-    def set_stream(self, stream_ptr: int):
-        self._check(lib.mxv_tab_set_stream(self._h, C.c_void_p(stream_ptr)))
 
 
 # Draw contract of the Blackjack engine's Philox streams (include/mxv.h RNG contract): 1 = rounds 2-4 (one card per word, consumed in the
@@ -1381,64 +1278,25 @@ class Tab:
 BJ_DRAW_CONTRACT = 2
 
 
-class Blackjack:
+class Blackjack(_Engine):
     """One mxv_bj handle: N device-resident Blackjack-v1 tables (see include/mxv.h)."""
+
+    _prefix = "mxv_bj"
 
     def __init__(self, num_envs, *, natural=False, sab=False, max_episode_steps=-1, device=0, env_offset=0, seed=0, action_seed=0):
         self.num_envs, self.device = int(num_envs), int(device)
         cfg = MxvBjConfig(self.device, int(bool(natural)), int(bool(sab)), int(max_episode_steps), self.num_envs,
-                          int(env_offset), int(seed) & (2**64 - 1), int(action_seed) & (2**64 - 1))
+                          int(env_offset), _u64(seed), _u64(action_seed))
         h = C.c_void_p()
-        rc = lib.mxv_bj_create(C.byref(cfg), C.byref(h))
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_bj_last_error(None) or b"").decode())
-        self._h = h
-        self._base_seed, self._per_env_seeds = int(seed) & (2**64 - 1), None
-        self._action_seed = int(action_seed) & (2**64 - 1)
-
-    def _check(self, rc: int):
-        if rc != OK:
-            raise MxvError(rc, (lib.mxv_bj_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.mxv_bj_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._adopt(lib.mxv_bj_create(C.byref(cfg), C.byref(h)), h)
+        self._init_seeds(seed, action_seed)
 
     def seed(self, base_seed: int, per_env_seeds=None, action_seed: int = 0):
-        p = None
-        if per_env_seeds is not None:
-            per_env_seeds = np.ascontiguousarray(per_env_seeds, dtype=np.uint64)
-            assert per_env_seeds.shape == (self.num_envs,)
-            p = per_env_seeds.ctypes.data
-        self._check(lib.mxv_bj_seed(self._h, int(base_seed) & (2**64 - 1), p, int(action_seed) & (2**64 - 1)))
-        self._base_seed = int(base_seed) & (2**64 - 1)
-        self._per_env_seeds = None if per_env_seeds is None else per_env_seeds.copy()
-        self._action_seed = int(action_seed) & (2**64 - 1)
-
-    def set_device_clock(self, on: bool = True):
-        """The step index in device memory, advanced on the stream: step / rollout calls become recordable in a caller's hipGraph."""
-        self._check(lib.mxv_bj_set_device_clock(self._h, 1 if on else 0))
-
-    def get_counters(self):
-        t, r = C.c_uint64(), C.c_uint32()
-        self._check(lib.mxv_bj_get_counters(self._h, C.byref(t), C.byref(r)))
-        return t.value, r.value
+        self._seed(base_seed, per_env_seeds, _u64(action_seed))
+        self._action_seed = _u64(action_seed)
 
     def snapshot(self) -> dict:
-        st, el = self.get_state()
-        t, r = self.get_counters()
-        on = getattr(self, "_stats_on", False)
-        return dict(num_envs=self.num_envs, state=st, elapsed=el, t=t, r=r, base_seed=self._base_seed,
-                    per_env_seeds=None if self._per_env_seeds is None else self._per_env_seeds.copy(),
-                    action_seed=self._action_seed, draw_contract=BJ_DRAW_CONTRACT, stats_on=on,
-                    running_returns=self.episode_stats_host(want_running=True)[2] if on else None)
+        return dict(super().snapshot(), draw_contract=BJ_DRAW_CONTRACT)
 
     def restore(self, snap: dict):
         if snap["num_envs"] != self.num_envs:
@@ -1497,27 +1355,6 @@ class Blackjack:
                                          trunc.ctypes.data, fin.ctypes.data))
         return obs, rew, term.view(np.bool_), trunc.view(np.bool_), fin
 
-    # -- episode statistics (gym.wrappers.RecordEpisodeStatistics fused into the kernels; include/mxv_toytext.h) --------------------------
-    def episode_stats(self, enable: bool = True):
-        self._check(lib.mxv_bj_episode_stats(self._h, 1 if enable else 0))
-        self._stats_on = bool(enable)
-
-    def set_episode_outputs(self, ep_return_dev=None, ep_length_dev=None):
-        """[N] / [K][N] device arrays (float32 returns, int32 lengths) the device-pointer calls fill where an episode ended; None detaches."""
-        self._check(lib.mxv_bj_set_episode_outputs(self._h, _ptr(ep_return_dev), _ptr(ep_length_dev)))
-
-    def episode_stats_host(self, want_running: bool = False):
-        """(returns, lengths[, running_returns]) of the last step_host call; valid where terminated | truncated."""
-        r = np.zeros(self.num_envs, dtype=np.float32)
-        l = np.zeros(self.num_envs, dtype=np.int32)
-        run = np.zeros(self.num_envs, dtype=np.float32) if want_running else None
-        self._check(lib.mxv_bj_episode_stats_host(self._h, r.ctypes.data, l.ctypes.data, _ptr(run)))
-        return (r, l, run) if want_running else (r, l)
-
-    def set_running_returns(self, running):
-        r = np.ascontiguousarray(running, dtype=np.float32).reshape(self.num_envs)
-        self._check(lib.mxv_bj_set_running_returns(self._h, r.ctypes.data))
-
     def get_state(self):
         st = np.empty(self.num_envs, np.int32)
         el = np.empty(self.num_envs, np.int32)
@@ -1528,9 +1365,3 @@ class Blackjack:
         st = None if state is None else np.ascontiguousarray(state, dtype=np.int32).reshape(self.num_envs)
         el = None if elapsed is None else np.ascontiguousarray(elapsed, dtype=np.int32).reshape(self.num_envs)
         self._check(lib.mxv_bj_set_state(self._h, _ptr(st), _ptr(el), int(t), int(r)))
-
-    def sync(self):
-        self._check(lib.mxv_bj_sync(self._h))
-
-    def set_stream(self, stream_ptr: int):
-        self._check(lib.mxv_bj_set_stream(self._h, C.c_void_p(stream_ptr)))

@@ -8,8 +8,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -18,6 +16,7 @@
 #include <tuple>
 #include <vector>
 
+#include "mxv_host.hpp"
 #include "mxv_kernels.hpp"
 #include "mxv_render.hpp"
 
@@ -28,8 +27,6 @@ namespace {
 constexpr int kStateDim[MXV_NUM_ENV_KINDS] = {4, 2, 4, 2, 2};
 constexpr int kObsDim[MXV_NUM_ENV_KINDS] = {4, 3, 6, 2, 2};
 constexpr int kNumActions[MXV_NUM_ENV_KINDS] = {2, 0, 3, 3, 0};
-
-thread_local std::string g_create_error;
 
 void default_params(int env_id, double *P) {
     std::memset(P, 0, sizeof(double) * MXV_MAX_PARAMS);
@@ -66,11 +63,11 @@ void default_bounds(int env_id, double *b) {
 
 }  // namespace
 
-struct mxv_handle {
+struct mxv_handle : mxv::HostCore {
+    static constexpr const char *kNullMessage = "NULL handle";
+    mxv_handle() : HostCore("mxv") {}
     mxv_config cfg{};
     int S = 0, O = 0, NA = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     double *state = nullptr;
     // mxv_adopt_obs: the caller's observation buffer doubles as the float32 half of the state (hilo_encode, mxv_kernels.hip)
     float *adopted_obs = nullptr;   // the buffer (caller-owned), or nullptr
@@ -79,30 +76,17 @@ struct mxv_handle {
     void *elapsed = nullptr;    // uint16 [N] when elapsed16, else int32 [N] (always n * 4 bytes allocated)
     bool elapsed16 = false;     // 0 < max_episode_steps <= 65535: the step kernels move 2 instead of 4 bytes each way
     uint32_t *episodes = nullptr;  // [N] resets of each env since seeding = index of its next draw from the reset stream
-    uint64_t *seeds = nullptr;  // optional per-env seeds
-    uint64_t *t_dev = nullptr;  // device-resident step index for graph replay
     double *ret_state = nullptr, *ret_part = nullptr;   // mxv_set_return_partials: NormalizeReward's running returns and their per-tile sums
     double ret_gamma = 0.0;
     double *obs_part = nullptr;        // mxv_set_obs_partials: where trajectory launches leave the observations' column sums (caller's memory)
     uint32_t *clock_ticket = nullptr;  // finished-workgroup counter of launches that advance the device clock themselves
-    bool dev_clock = false;     // mxv_set_device_clock: every launch reads the step index from t_dev and a one-thread kernel advances it
-    int32_t *err = nullptr;     // latched kernel error word
-    uint64_t base_seed = 0, action_seed = 0;
-    uint64_t t = 0;
-    uint32_t r = 0;
-    bool was_reset = false;
     bool state_injected = false;  // set by mxv_set_state / unusual reset bounds, consumed by the next step launch
     bool state_out_of_range = false;  // Pendulum only: an injected angle beyond the unguarded range stays until a full reset
     LaunchInfo last_launch{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // mxv_last_launch
     bool step_noise = false;      // Acrobot torque_noise_max > 0 (acrobot.py:202-205): the step draws from the step-noise stream
     EnvParams P{};
     bool default_params = true;
-    float *ep_acc = nullptr;        // running episode returns when episode statistics are enabled
     uint8_t *beyond = nullptr;      // CartPole + MXV_FLAG_NO_AUTORESET: per-env "terminated before" marks (cartpole.py:169-184)
-    float *ep_return_out = nullptr; // caller-attached outputs of the statistics (device)
-    int32_t *ep_length_out = nullptr;
-    float *st_ep_r = nullptr;       // staging for mxv_step_host / mxv_episode_stats_host
-    int32_t *st_ep_l = nullptr;
     double *params_pe = nullptr;  // [MXV_MAX_PARAMS][N] when per-env physics parameters are active
     int param_mode() const { return params_pe ? PM_PER_ENV : (default_params ? PM_DEFAULT : PM_BROADCAST); }
     double bounds[2] = {0, 0};
@@ -144,7 +128,6 @@ struct mxv_handle {
     uint8_t *snap_term = nullptr, *snap_trunc = nullptr;
     hipEvent_t ev_wait = nullptr;   // mxv_wait_stream
     hipEvent_t ev_mixed = nullptr;  // orders this handle's stream against a mixed-batch launch issued on another handle's stream
-    std::string error;
 
     size_t action_bytes() const {
         if (NA > 0) return (cfg.flags & MXV_FLAG_ACTION_I32) ? 4 : 8;
@@ -155,39 +138,10 @@ struct mxv_handle {
 
 namespace {
 
-int fail(mxv_handle *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h)
-        h->error = buf;
-    else
-        g_create_error = buf;
-    return code;
-}
-
-#define MXV_HIP(h, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return fail((h), MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-#define MXV_CHECK_HANDLE(h) \
-    if (!(h)) return fail(nullptr, MXV_ERR_INVALID_ARG, "NULL handle")
-
-int use_device(mxv_handle *h) {
-    MXV_HIP(h, hipSetDevice(h->cfg.device));
-    return MXV_OK;
-}
-
 int check_latched(mxv_handle *h) {
     int32_t e = 0;
-    MXV_HIP(h, hipMemcpyAsync(&e, h->err, sizeof e, hipMemcpyDeviceToHost, h->stream));
-    MXV_HIP(h, hipStreamSynchronize(h->stream));
+    if (int rc = take_latched(h, &e)) return rc;
     if (e != 0) {
-        MXV_HIP(h, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
         if (e & 1)
             return fail(h, MXV_ERR_INVALID_ACTION, "discrete action outside [0, %d) (Discrete.contains assert)", h->NA);
         if (e & kRenderIndexErrorBit)
@@ -213,15 +167,7 @@ int take_block_error(mxv_handle *h) {  // after the stream drained
     return fail(h, MXV_ERR_INVALID_ARG, "kernel error word 0x%x", e);
 }
 
-// The handle has just launched `delta` vector steps (negative: a step that is being taken back).  Device-clock mode: the device word
-// follows through a one-thread kernel on the same stream — captured with the launch when a caller's hipGraph is being recorded.
-constexpr int64_t kClockInKernelEnvs = 65536;
-
-int clock_add(mxv_handle *h, int64_t delta) {
-    h->t += (uint64_t)delta;
-    if (h->dev_clock) MXV_HIP(h, launch_add_word(h->t_dev, (uint64_t)delta, h->stream));
-    return MXV_OK;
-}
+constexpr int64_t kClockInKernelEnvs = 65536;   // see do_step
 
 void fill_step_args(mxv_handle *h, StepArgs &a) {
     a.state = h->state;
@@ -294,14 +240,8 @@ int ensure_f64(mxv_handle *h) {
     return MXV_OK;
 }
 
-// Every caller-owned tensor a launch touches must sit on its element's natural boundary (observations: the row's vector width — the kernels
-// store them as float4 / float2).  An odd address would not fault on this device (unaligned global access is enabled) but tears every
-// coalesced burst, and it is a caller bug either way: refused up front with the name of the tensor (tests/c_consumer/abi_fuzz.c).
-int check_aligned(mxv_handle *h, const void *p, size_t bytes, const char *what) {
-    if (p && ((uintptr_t)p & (bytes - 1)) != 0)
-        return fail(h, MXV_ERR_INVALID_ARG, "%s pointer %p is not %zu-byte aligned", what, p, bytes);
-    return MXV_OK;
-}
+// Every caller-owned tensor a launch touches must sit on its element's natural boundary (check_aligned; observations: the row's vector
+// width — the kernels store them as float4 / float2).
 int check_step_buffers(mxv_handle *h, const StepArgs &a) {
     const size_t obs_al = h->O == 4 ? 16 : ((h->O % 2 == 0) ? 8 : 4);
     const size_t act_al = h->NA > 0 ? ((a.flags & MXV_FLAG_ACTION_I32) ? 4 : 8) : 4, rew_al = (a.flags & MXV_FLAG_REWARD_F32) ? 4 : 8;
@@ -595,30 +535,32 @@ int mxv_default_reset_bounds(int32_t env_id, double *bounds2_host) {
     return MXV_OK;
 }
 
-const char *mxv_last_error(const mxv_handle *h) { return h ? h->error.c_str() : g_create_error.c_str(); }
+const char *mxv_last_error(const mxv_handle *h) { return last_error(h); }
 
 int mxv_create(const mxv_config *cfg, mxv_handle **out) {
-    if (!cfg || !out) return fail(nullptr, MXV_ERR_INVALID_ARG, "NULL config or output pointer");
+    if (!cfg || !out) return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "NULL config or output pointer");
     *out = nullptr;
     if (cfg->env_id < 0 || cfg->env_id >= MXV_NUM_ENV_KINDS)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "unknown env_id %d", cfg->env_id);
-    if (cfg->num_envs <= 0) return fail(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be positive (got %lld)", (long long)cfg->num_envs);
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "unknown env_id %d", cfg->env_id);
+    if (cfg->num_envs <= 0) return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be positive (got %lld)", (long long)cfg->num_envs);
     // the fused kernels address one step's slice of every output array with 32-bit byte offsets (16 B per env at most)
     if (cfg->num_envs > MXV_MAX_NUM_ENVS)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "num_envs %lld exceeds the per-handle maximum of %lld: shard the vector env (env_offset)",
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "num_envs %lld exceeds the per-handle maximum of %lld: shard the vector env (env_offset)",
                     (long long)cfg->num_envs, (long long)MXV_MAX_NUM_ENVS);
     if (cfg->env_offset < 0 || cfg->env_offset % MXV_ENV_ALIGN != 0)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "env_offset must be a non-negative multiple of %d", MXV_ENV_ALIGN);
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "env_offset must be a non-negative multiple of %d", MXV_ENV_ALIGN);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
-        return fail(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
+        return fail<mxv_handle>(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
                     e != hipSuccess ? hipGetErrorString(e) : "device count 0");
     if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range (%d devices)", cfg->device, ndev);
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range (%d devices)", cfg->device, ndev);
     mxv_handle *h = new (std::nothrow) mxv_handle();
-    if (!h) return fail(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
+    if (!h) return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
     h->cfg = *cfg;
+    h->device = cfg->device;
+    h->num_envs = cfg->num_envs;
     h->S = kStateDim[cfg->env_id];
     h->O = kObsDim[cfg->env_id];
     h->NA = kNumActions[cfg->env_id];
@@ -627,87 +569,57 @@ int mxv_create(const mxv_config *cfg, mxv_handle **out) {
     default_params(cfg->env_id, h->P.p);
     default_bounds(cfg->env_id, h->bounds);
     const size_t n = (size_t)cfg->num_envs;
-#define MXV_CREATE_HIP(expr)                                                                \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            fail(nullptr, MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));             \
-            mxv_destroy(h);                                                                 \
-            return MXV_ERR_HIP;                                                             \
-        }                                                                                   \
-    } while (0)
-    MXV_CREATE_HIP(hipSetDevice(cfg->device));
-    MXV_CREATE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    MXV_CREATE_HIP(h, mxv_destroy, hipSetDevice(cfg->device));
+    MXV_CREATE_HIP(h, mxv_destroy, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
-    MXV_CREATE_HIP(hipMalloc((void **)&h->state, n * h->S * sizeof(double)));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->state, n * h->S * sizeof(double)));
     h->elapsed16 = cfg->max_episode_steps > 0 && cfg->max_episode_steps <= 65535 && !getenv("MXV_ELAPSED32");   // (A/B hook)
-    MXV_CREATE_HIP(hipMalloc((void **)&h->elapsed, n * sizeof(int32_t)));
-    MXV_CREATE_HIP(hipMalloc((void **)&h->episodes, n * sizeof(uint32_t)));
-    MXV_CREATE_HIP(hipMalloc((void **)&h->t_dev, sizeof(uint64_t)));
-    MXV_CREATE_HIP(hipMalloc((void **)&h->clock_ticket, sizeof(uint32_t)));
-    MXV_CREATE_HIP(hipMalloc((void **)&h->err, sizeof(int32_t)));
-    MXV_CREATE_HIP(hipMemsetAsync(h->state, 0, n * h->S * sizeof(double), h->stream));
-    MXV_CREATE_HIP(hipMemsetAsync(h->elapsed, 0, n * sizeof(int32_t), h->stream));
-    MXV_CREATE_HIP(hipMemsetAsync(h->episodes, 0, n * sizeof(uint32_t), h->stream));
-    MXV_CREATE_HIP(hipMemsetAsync(h->t_dev, 0, sizeof(uint64_t), h->stream));
-    MXV_CREATE_HIP(hipMemsetAsync(h->clock_ticket, 0, sizeof(uint32_t), h->stream));
-    MXV_CREATE_HIP(hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->elapsed, n * sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->episodes, n * sizeof(uint32_t)));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->t_dev, sizeof(uint64_t)));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->clock_ticket, sizeof(uint32_t)));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->err, sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->state, 0, n * h->S * sizeof(double), h->stream));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->elapsed, 0, n * sizeof(int32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->episodes, 0, n * sizeof(uint32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->t_dev, 0, sizeof(uint64_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->clock_ticket, 0, sizeof(uint32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
     if (cfg->env_id == MXV_CARTPOLE && (cfg->flags & MXV_FLAG_NO_AUTORESET)) {   // steps_beyond_terminated marks (cartpole.py:169-184)
-        MXV_CREATE_HIP(hipMalloc((void **)&h->beyond, n));
-        MXV_CREATE_HIP(hipMemsetAsync(h->beyond, 0, n, h->stream));
+        MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->beyond, n));
+        MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->beyond, 0, n, h->stream));
     }
-    MXV_CREATE_HIP(hipStreamSynchronize(h->stream));
-#undef MXV_CREATE_HIP
+    MXV_CREATE_HIP(h, mxv_destroy, hipStreamSynchronize(h->stream));
     *out = h;
     return MXV_OK;
 }
 
 int mxv_destroy(mxv_handle *h) {
     if (!h) return MXV_OK;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    drain(h);
     (void)mxv_comm_destroy(h);
     if (h->ev_mixed) (void)hipEventDestroy(h->ev_mixed);
     if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
     free_graphs(h);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->fin_host) (void)hipHostFree(h->fin_host);
-    if (h->fin_dev) (void)hipFree(h->fin_dev);
-    void *bufs[] = {h->lo, h->state, h->elapsed, h->episodes, h->seeds, h->t_dev, h->clock_ticket, h->err, h->params_pe, h->ep_acc, h->st_ep_r, h->st_ep_l, h->dv_block,
-                    h->beyond};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    free_core(h, {h->fin_dev, h->lo, h->state, h->elapsed, h->episodes, h->clock_ticket, h->params_pe, h->dv_block, h->beyond});
     delete h;
     return MXV_OK;
 }
 
 int mxv_seed(mxv_handle *h, uint64_t base_seed, const uint64_t *per_env_seeds_host) {
-    MXV_CHECK_HANDLE(h);
-    if (int rc = use_device(h)) return rc;
-    MXV_HIP(h, hipStreamSynchronize(h->stream));
+    MXV_CHECK(h);
+    const int rc = reseed(h, base_seed, per_env_seeds_host);
     free_graphs(h);  // captured kernel arguments hold the old seeds
-    h->base_seed = base_seed;
-    h->t = 0;
-    h->r = 0;
-    if (h->dev_clock) MXV_HIP(h, launch_set_word(h->t_dev, 0, h->stream));
+    if (rc) return rc;
     // a (re)seeded env starts its reset stream from the beginning: reset ordinals back to 0
     MXV_HIP(h, hipMemsetAsync(h->episodes, 0, (size_t)h->cfg.num_envs * sizeof(uint32_t), h->stream));
-    if (per_env_seeds_host) {
-        const size_t bytes = (size_t)h->cfg.num_envs * sizeof(uint64_t);
-        if (!h->seeds) MXV_HIP(h, hipMalloc((void **)&h->seeds, bytes));
-        MXV_HIP(h, hipMemcpyAsync(h->seeds, per_env_seeds_host, bytes, hipMemcpyHostToDevice, h->stream));
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-    } else if (h->seeds) {
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-        MXV_HIP(h, hipFree(h->seeds));
-        h->seeds = nullptr;
-    }
     return MXV_OK;
 }
 
 int mxv_seed_actions(mxv_handle *h, uint64_t action_seed) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     MXV_HIP(h, hipStreamSynchronize(h->stream));
     free_graphs(h);
@@ -716,20 +628,20 @@ int mxv_seed_actions(mxv_handle *h, uint64_t action_seed) {
 }
 
 int mxv_reset(mxv_handle *h, const uint8_t *mask_dev, const double *bounds2_host, float *obs_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     return do_reset(h, mask_dev, bounds2_host, obs_dev);
 }
 
 int mxv_step(mxv_handle *h, const void *actions_dev, float *obs_dev, void *reward_dev, uint8_t *terminated_dev,
              uint8_t *truncated_dev, float *final_obs_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!actions_dev) return fail(h, MXV_ERR_INVALID_ARG, "actions pointer is NULL (use mxv_step_sampled)");
     return do_step(h, actions_dev, nullptr, obs_dev, reward_dev, terminated_dev, truncated_dev, final_obs_dev);
 }
 
 int mxv_step_sampled(mxv_handle *h, void *actions_out_dev, float *obs_dev, void *reward_dev, uint8_t *terminated_dev,
                      uint8_t *truncated_dev, float *final_obs_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     return do_step(h, nullptr, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, final_obs_dev);
 }
 
@@ -808,7 +720,7 @@ extern "C" {
 
 int mxv_rollout(mxv_handle *h, int32_t K, int32_t per_step, int32_t mode, void *actions_out_dev, float *obs_dev,
                 void *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, float *final_obs_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = rollout_checks(h, K, obs_dev)) return rc;
     if (mode == MXV_ROLLOUT_FUSED)
         return fused_launch(h, K, per_step, nullptr, actions_out_dev, obs_dev, reward_dev, terminated_dev,
@@ -880,7 +792,7 @@ int mxv_rollout(mxv_handle *h, int32_t K, int32_t per_step, int32_t mode, void *
 }
 
 int mxv_set_final_snapshot(mxv_handle *h, float *obs_dev, void *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!obs_dev && (reward_dev || terminated_dev || truncated_dev))
         return fail(h, MXV_ERR_INVALID_ARG, "mxv_set_final_snapshot: the observation buffer is required (NULL everything to detach)");
     h->snap_obs = obs_dev;
@@ -892,7 +804,7 @@ int mxv_set_final_snapshot(mxv_handle *h, float *obs_dev, void *reward_dev, uint
 
 int mxv_rollout_tape(mxv_handle *h, int32_t K, int32_t per_step, const void *actions_tape_dev, float *obs_dev,
                      void *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, float *final_obs_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!actions_tape_dev) return fail(h, MXV_ERR_INVALID_ARG, "actions tape pointer is NULL");
     if (int rc = rollout_checks(h, K, obs_dev)) return rc;
     return fused_launch(h, K, per_step, actions_tape_dev, nullptr, obs_dev, reward_dev, terminated_dev, truncated_dev,
@@ -900,7 +812,7 @@ int mxv_rollout_tape(mxv_handle *h, int32_t K, int32_t per_step, const void *act
 }
 
 int mxv_sample_actions(mxv_handle *h, void *actions_out_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!actions_out_dev) return fail(h, MXV_ERR_INVALID_ARG, "actions_out pointer is NULL");
     if (int rc = use_device(h)) return rc;
     SampleArgs a{};
@@ -923,7 +835,7 @@ int mxv_sample_actions(mxv_handle *h, void *actions_out_dev) {
 }
 
 int mxv_reset_host(mxv_handle *h, const uint8_t *mask_host, const double *bounds2_host, float *obs_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_staging(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
@@ -944,7 +856,7 @@ int mxv_reset_host(mxv_handle *h, const uint8_t *mask_host, const double *bounds
 
 int mxv_step_host(mxv_handle *h, const void *actions_host, float *obs_host, void *reward_host, uint8_t *terminated_host,
                   uint8_t *truncated_host, float *final_obs_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!actions_host || !obs_host) return fail(h, MXV_ERR_INVALID_ARG, "actions/obs pointer is NULL");
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_staging(h)) return rc;
@@ -1001,7 +913,7 @@ int mxv_step_host(mxv_handle *h, const void *actions_host, float *obs_host, void
 }
 
 int mxv_staging_view(mxv_handle *h, const float **obs, const void **reward, const uint8_t **terminated, const uint8_t **truncated) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->st_obs) return fail(h, MXV_ERR_INVALID_ARG, "mxv_staging_view: no host step or reset has run on this handle yet");
     if (obs) *obs = h->st_obs;
     if (reward) *reward = h->st_reward;
@@ -1011,19 +923,19 @@ int mxv_staging_view(mxv_handle *h, const float **obs, const void **reward, cons
 }
 
 int mxv_host_alloc(size_t bytes, void **ptr) {
-    if (!ptr || bytes == 0) return fail(nullptr, MXV_ERR_INVALID_ARG, "mxv_host_alloc: NULL pointer or zero size");
-    MXV_HIP(nullptr, hipHostMalloc(ptr, bytes, hipHostMallocPortable));
+    if (!ptr || bytes == 0) return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "mxv_host_alloc: NULL pointer or zero size");
+    MXV_HIP((mxv_handle *)nullptr, hipHostMalloc(ptr, bytes, hipHostMallocPortable));
     return MXV_OK;
 }
 
 int mxv_host_free(void *ptr) {
-    if (ptr) MXV_HIP(nullptr, hipHostFree(ptr));
+    if (ptr) MXV_HIP((mxv_handle *)nullptr, hipHostFree(ptr));
     return MXV_OK;
 }
 
 int mxv_host_block_layout(mxv_handle *h, size_t *bytes, size_t *final_obs_off, size_t *obs_off, size_t *reward_off,
                           size_t *terminated_off, size_t *truncated_off) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_staging(h)) return rc;
     const char *base = (const char *)h->st_final;
@@ -1037,7 +949,7 @@ int mxv_host_block_layout(mxv_handle *h, size_t *bytes, size_t *final_obs_off, s
 }
 
 int mxv_step_host_block(mxv_handle *h, const void *actions_host, void *block_host, int32_t want_final) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!actions_host || !block_host) return fail(h, MXV_ERR_INVALID_ARG, "actions/block pointer is NULL");
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_staging(h)) return rc;
@@ -1080,7 +992,7 @@ int mxv_step_host_block(mxv_handle *h, const void *actions_host, void *block_hos
 
 int mxv_host_io(mxv_handle *h, void **actions, float **obs, void **reward, uint8_t **terminated, uint8_t **truncated,
                 float **final_obs) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_staging(h, /*want_pinned=*/true)) return rc;
     const ptrdiff_t shift = (char *)h->hm_block - (char *)(h->hostmap ? h->hm_block : h->dv_block);  // same layout
@@ -1124,7 +1036,7 @@ int mapped_finish(mxv_handle *h, bool stepped) {
 extern "C" {
 
 int mxv_step_mapped(mxv_handle *h) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->hm_block) return fail(h, MXV_ERR_INVALID_ARG, "call mxv_host_io() first: the mapped I/O block does not exist yet");
     if (int rc = use_device(h)) return rc;
     if (!h->hostmap)
@@ -1147,7 +1059,7 @@ int mxv_step_mapped(mxv_handle *h) {
 }
 
 int mxv_reset_mapped(mxv_handle *h, const double *bounds2_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->hm_block) return fail(h, MXV_ERR_INVALID_ARG, "call mxv_host_io() first: the mapped I/O block does not exist yet");
     if (int rc = use_device(h)) return rc;
     if (int rc = do_reset(h, nullptr, bounds2_host, h->st_obs)) return rc;
@@ -1156,7 +1068,7 @@ int mxv_reset_mapped(mxv_handle *h, const double *bounds2_host) {
 
 /* see include/mxv.h */
 int mxv_adopt_obs(mxv_handle *h, float *obs_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_f64(h)) return rc;            // whatever was adopted before hands the state back first
     if (!obs_dev) {
@@ -1173,7 +1085,7 @@ int mxv_adopt_obs(mxv_handle *h, float *obs_dev) {
 }
 
 int mxv_get_state(mxv_handle *h, double *state_soa_host, int32_t *elapsed_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_f64(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
@@ -1194,7 +1106,7 @@ int mxv_get_state(mxv_handle *h, double *state_soa_host, int32_t *elapsed_host) 
 }
 
 int mxv_set_state(mxv_handle *h, const double *state_soa_host, const int32_t *elapsed_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_f64(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
@@ -1244,7 +1156,7 @@ int mxv_set_state(mxv_handle *h, const double *state_soa_host, const int32_t *el
 }
 
 int mxv_last_launch(mxv_handle *h, mxv_launch_info *out) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!out) return fail(h, MXV_ERR_INVALID_ARG, "mxv_last_launch: out is NULL");
     static_assert(sizeof(mxv_launch_info) == sizeof(LaunchInfo), "mxv_launch_info mirrors LaunchInfo member for member");
     std::memcpy(out, &h->last_launch, sizeof(*out));
@@ -1252,36 +1164,23 @@ int mxv_last_launch(mxv_handle *h, mxv_launch_info *out) {
 }
 
 int mxv_get_counters(mxv_handle *h, uint64_t *t, uint32_t *r) {
-    MXV_CHECK_HANDLE(h);
-    if (h->dev_clock) {  // graphs the caller replays advance the device word only: read it (synchronises the handle's stream)
-        if (int rc = use_device(h)) return rc;
-        MXV_HIP(h, hipMemcpyAsync(&h->t, h->t_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (t) *t = h->t;
-    if (r) *r = h->r;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return get_counters(h, t, r);
 }
 
 int mxv_set_counters(mxv_handle *h, uint64_t t, uint32_t r) {
-    MXV_CHECK_HANDLE(h);
-    h->t = t;
-    h->r = r;
-    if (h->dev_clock) {
-        if (int rc = use_device(h)) return rc;
-        MXV_HIP(h, launch_set_word(h->t_dev, h->t, h->stream));
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_counters(h, t, r);
 }
 
 int mxv_set_obs_partials(mxv_handle *h, double *partials_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     h->obs_part = partials_dev;
     return MXV_OK;
 }
 
 int mxv_set_return_partials(mxv_handle *h, double *returns_state_dev, double gamma, double *partials_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (partials_dev && !returns_state_dev) return fail(h, MXV_ERR_INVALID_ARG, "mxv_set_return_partials: the running returns [N] are required");
     h->ret_part = partials_dev;
     h->ret_state = partials_dev ? returns_state_dev : nullptr;
@@ -1290,7 +1189,7 @@ int mxv_set_return_partials(mxv_handle *h, double *returns_state_dev, double gam
 }
 
 int mxv_obs_partials_layout(mxv_handle *h, int64_t *leaves, int64_t *envs_per_leaf, int32_t *values) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     const int64_t per = stats_leaf_envs(h->cfg.env_id);
     if (leaves) *leaves = (h->cfg.num_envs + per - 1) / per;
     if (envs_per_leaf) *envs_per_leaf = per;
@@ -1299,25 +1198,16 @@ int mxv_obs_partials_layout(mxv_handle *h, int64_t *leaves, int64_t *envs_per_le
 }
 
 int mxv_set_device_clock(mxv_handle *h, int32_t on) {
-    MXV_CHECK_HANDLE(h);
-    if (int rc = use_device(h)) return rc;
-    if (on && !h->dev_clock) {
-        MXV_HIP(h, launch_set_word(h->t_dev, h->t, h->stream));
-        h->dev_clock = true;
-    } else if (!on && h->dev_clock) {
-        MXV_HIP(h, hipMemcpyAsync(&h->t, h->t_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-        h->dev_clock = false;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_device_clock(h, on);
 }
 
 int mxv_write_probe(int32_t device, int64_t num_envs, int32_t K, int32_t launches, float *obs_dev, double *reward_dev, int64_t *actions_dev,
                     uint8_t *terminated_dev, uint8_t *truncated_dev, double *us_per_step) {
     if (!obs_dev || !reward_dev || !actions_dev || !terminated_dev || !truncated_dev || !us_per_step || K < 1 || launches < 1 ||
         num_envs < 1024 || num_envs % 1024 != 0)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "mxv_write_probe: [K][num_envs] buffers of all five outputs, num_envs a multiple of 1024");
-    MXV_HIP(nullptr, hipSetDevice(device));
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "mxv_write_probe: [K][num_envs] buffers of all five outputs, num_envs a multiple of 1024");
+    MXV_HIP((mxv_handle *)nullptr, hipSetDevice(device));
     hipStream_t s = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -1335,7 +1225,7 @@ int mxv_write_probe(int32_t device, int64_t num_envs, int32_t K, int32_t launche
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (s) (void)hipStreamDestroy(s);
-    if (err != hipSuccess) return fail(nullptr, MXV_ERR_HIP, "mxv_write_probe: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return fail<mxv_handle>(nullptr, MXV_ERR_HIP, "mxv_write_probe: %s", hipGetErrorString(err));
     *us_per_step = (double)ms * 1e3 / ((double)launches * K);
     return MXV_OK;
 }
@@ -1344,8 +1234,8 @@ int mxv_write_probe_env(int32_t device, int32_t env_id, int32_t flags, int64_t n
                         void *reward_dev, void *actions_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, double *us_per_step) {
     if (!obs_dev || !reward_dev || !actions_dev || !terminated_dev || !truncated_dev || !us_per_step || K < 1 || launches < 1 || num_envs < 1 ||
         env_id < 0 || env_id >= MXV_NUM_ENV_KINDS)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "mxv_write_probe_env: [K][num_envs] buffers of all five outputs and a valid env kind");
-    MXV_HIP(nullptr, hipSetDevice(device));
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "mxv_write_probe_env: [K][num_envs] buffers of all five outputs and a valid env kind");
+    MXV_HIP((mxv_handle *)nullptr, hipSetDevice(device));
     hipStream_t s = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -1363,13 +1253,13 @@ int mxv_write_probe_env(int32_t device, int32_t env_id, int32_t flags, int64_t n
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (s) (void)hipStreamDestroy(s);
-    if (err != hipSuccess) return fail(nullptr, MXV_ERR_HIP, "mxv_write_probe_env: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return fail<mxv_handle>(nullptr, MXV_ERR_HIP, "mxv_write_probe_env: %s", hipGetErrorString(err));
     *us_per_step = (double)ms * 1e3 / ((double)launches * K);
     return MXV_OK;
 }
 
 int mxv_final_packed(mxv_handle *h, int32_t enable, int32_t *supported) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     if (int rc = ensure_staging(h)) return rc;
     const bool ok = !h->hostmap;  // small envs: the kernel writes final_obs straight into the pinned block, nothing to pack
@@ -1379,7 +1269,7 @@ int mxv_final_packed(mxv_handle *h, int32_t enable, int32_t *supported) {
 }
 
 int mxv_final_packed_view(mxv_handle *h, const int32_t **count, const int32_t **idx, const float **rows) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->fin_host) return fail(h, MXV_ERR_INVALID_ARG, "mxv_final_packed_view: packed final rows exist for large envs only (see mxv_final_packed)");
     const FinLayout L((size_t)h->cfg.num_envs, (size_t)h->O);
     if (count) *count = (const int32_t *)h->fin_host;
@@ -1389,7 +1279,7 @@ int mxv_final_packed_view(mxv_handle *h, const int32_t **count, const int32_t **
 }
 
 int mxv_final_packed_stats_view(mxv_handle *h, const float **ep_return, const int32_t **ep_length) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->fin_host) return fail(h, MXV_ERR_INVALID_ARG, "mxv_final_packed_stats_view: packed records exist for large envs only (see mxv_final_packed)");
     const FinLayout L((size_t)h->cfg.num_envs, (size_t)h->O);
     if (ep_return) *ep_return = (const float *)(h->fin_host + L.ep_r);
@@ -1398,7 +1288,7 @@ int mxv_final_packed_stats_view(mxv_handle *h, const float **ep_return, const in
 }
 
 int mxv_get_episodes(mxv_handle *h, uint32_t *episodes_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!episodes_host) return fail(h, MXV_ERR_INVALID_ARG, "episodes pointer is NULL");
     if (int rc = use_device(h)) return rc;
     MXV_HIP(h, hipMemcpyAsync(episodes_host, h->episodes, (size_t)h->cfg.num_envs * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1407,7 +1297,7 @@ int mxv_get_episodes(mxv_handle *h, uint32_t *episodes_host) {
 }
 
 int mxv_set_episodes(mxv_handle *h, const uint32_t *episodes_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!episodes_host) return fail(h, MXV_ERR_INVALID_ARG, "episodes pointer is NULL");
     if (int rc = use_device(h)) return rc;
     MXV_HIP(h, hipMemcpyAsync(h->episodes, episodes_host, (size_t)h->cfg.num_envs * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -1419,7 +1309,7 @@ int mxv_set_episodes(mxv_handle *h, const uint32_t *episodes_host) {
 // keep paying 0.0, not 1.0 once more.  Handles that carry no marks (any other configuration): get fills zeros, set accepts
 // all-zero marks only.
 int mxv_get_beyond(mxv_handle *h, uint8_t *beyond_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!beyond_host) return fail(h, MXV_ERR_INVALID_ARG, "beyond pointer is NULL");
     const size_t n = (size_t)h->cfg.num_envs;
     if (!h->beyond) {
@@ -1433,7 +1323,7 @@ int mxv_get_beyond(mxv_handle *h, uint8_t *beyond_host) {
 }
 
 int mxv_set_beyond(mxv_handle *h, const uint8_t *beyond_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!beyond_host) return fail(h, MXV_ERR_INVALID_ARG, "beyond pointer is NULL");
     const size_t n = (size_t)h->cfg.num_envs;
     if (!h->beyond) {
@@ -1448,14 +1338,14 @@ int mxv_set_beyond(mxv_handle *h, const uint8_t *beyond_host) {
 }
 
 int mxv_get_params(mxv_handle *h, double *params_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!params_host) return fail(h, MXV_ERR_INVALID_ARG, "params pointer is NULL");
     std::memcpy(params_host, h->P.p, sizeof h->P.p);
     return MXV_OK;
 }
 
 int mxv_set_params(mxv_handle *h, const double *params_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!params_host) return fail(h, MXV_ERR_INVALID_ARG, "params pointer is NULL");
     if (h->cfg.env_id == MXV_ACROBOT && params_host[10] < 0.0)
         return fail(h, MXV_ERR_INVALID_ARG, "Acrobot torque_noise_max must be >= 0");
@@ -1475,7 +1365,7 @@ int mxv_set_params(mxv_handle *h, const double *params_host) {
 }
 
 int mxv_set_params_per_env(mxv_handle *h, const double *params_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!params_host) return fail(h, MXV_ERR_INVALID_ARG, "params pointer is NULL");
     const size_t n = (size_t)h->cfg.num_envs;
     bool noise = false;
@@ -1497,7 +1387,7 @@ int mxv_set_params_per_env(mxv_handle *h, const double *params_host) {
 }
 
 int mxv_get_params_per_env(mxv_handle *h, double *params_host) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!params_host) return fail(h, MXV_ERR_INVALID_ARG, "params pointer is NULL");
     const size_t n = (size_t)h->cfg.num_envs;
     if (!h->params_pe) {
@@ -1512,83 +1402,46 @@ int mxv_get_params_per_env(mxv_handle *h, double *params_host) {
 }
 
 int mxv_episode_stats(mxv_handle *h, int32_t enable) {
-    MXV_CHECK_HANDLE(h);
-    if (int rc = use_device(h)) return rc;
-    MXV_HIP(h, hipStreamSynchronize(h->stream));
-    free_graphs(h);
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (enable && !h->ep_acc) {
-        if (h->cfg.flags & MXV_FLAG_NO_AUTORESET)
-            return fail(h, MXV_ERR_UNSUPPORTED, "episode statistics need autoreset (episode length is the TimeLimit counter)");
-        MXV_HIP(h, hipMalloc((void **)&h->ep_acc, n * sizeof(float)));
-        MXV_HIP(h, hipMalloc((void **)&h->st_ep_r, n * sizeof(float)));
-        MXV_HIP(h, hipMalloc((void **)&h->st_ep_l, n * sizeof(int32_t)));
-        MXV_HIP(h, hipMemsetAsync(h->ep_acc, 0, n * sizeof(float), h->stream));
-        MXV_HIP(h, hipMemsetAsync(h->st_ep_r, 0, n * sizeof(float), h->stream));
-        MXV_HIP(h, hipMemsetAsync(h->st_ep_l, 0, n * sizeof(int32_t), h->stream));
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-    } else if (!enable && h->ep_acc) {
-        MXV_HIP(h, hipFree(h->ep_acc));
-        MXV_HIP(h, hipFree(h->st_ep_r));
-        MXV_HIP(h, hipFree(h->st_ep_l));
-        h->ep_acc = nullptr;
-        h->st_ep_r = nullptr;
-        h->st_ep_l = nullptr;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    if (enable && !h->ep_acc && (h->cfg.flags & MXV_FLAG_NO_AUTORESET))
+        return fail(h, MXV_ERR_UNSUPPORTED, "episode statistics need autoreset (episode length is the TimeLimit counter)");
+    const int rc = episode_stats(h, enable);
+    free_graphs(h);  // captured kernel arguments hold the old pointers
+    return rc;
 }
 
 int mxv_set_episode_outputs(mxv_handle *h, float *ep_return_dev, int32_t *ep_length_dev) {
-    MXV_CHECK_HANDLE(h);
-    if (int rc = use_device(h)) return rc;
-    MXV_HIP(h, hipStreamSynchronize(h->stream));
+    MXV_CHECK(h);
+    const int rc = set_episode_outputs(h, ep_return_dev, ep_length_dev);
     free_graphs(h);  // captured kernel arguments hold the old pointers
-    h->ep_return_out = ep_return_dev;
-    h->ep_length_out = ep_length_dev;
-    return MXV_OK;
+    return rc;
 }
 
 int mxv_episode_stats_host(mxv_handle *h, float *ep_return_host, int32_t *ep_length_host, float *running_return_host) {
-    MXV_CHECK_HANDLE(h);
-    if (!h->ep_acc) return fail(h, MXV_ERR_INVALID_ARG, "episode statistics are not enabled (mxv_episode_stats)");
-    if (int rc = use_device(h)) return rc;
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (ep_return_host)
-        MXV_HIP(h, hipMemcpyAsync(ep_return_host, h->st_ep_r, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (ep_length_host)
-        MXV_HIP(h, hipMemcpyAsync(ep_length_host, h->st_ep_l, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (running_return_host)
-        MXV_HIP(h, hipMemcpyAsync(running_return_host, h->ep_acc, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    MXV_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return episode_stats_host(h, ep_return_host, ep_length_host, running_return_host);
 }
 
 int mxv_set_running_returns(mxv_handle *h, const float *running_return_host) {
-    MXV_CHECK_HANDLE(h);
-    if (!h->ep_acc) return fail(h, MXV_ERR_INVALID_ARG, "episode statistics are not enabled (mxv_episode_stats)");
-    if (!running_return_host) return fail(h, MXV_ERR_INVALID_ARG, "running_return pointer is NULL");
-    if (int rc = use_device(h)) return rc;
-    MXV_HIP(h, hipMemcpyAsync(h->ep_acc, running_return_host, (size_t)h->cfg.num_envs * sizeof(float), hipMemcpyHostToDevice,
-                              h->stream));
-    MXV_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_running_returns(h, running_return_host);
 }
 
 int mxv_sync(mxv_handle *h) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (int rc = use_device(h)) return rc;
     return check_latched(h);
 }
 
 int mxv_get_stream(mxv_handle *h, void **stream) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!stream) return fail(h, MXV_ERR_INVALID_ARG, "stream pointer is NULL");
     *stream = (void *)h->stream;
     return MXV_OK;
 }
 
 int mxv_wait_stream(mxv_handle *h, void *other_stream) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if ((hipStream_t)other_stream == h->stream) return MXV_OK;
     if (int rc = use_device(h)) return rc;
     if (!h->ev_wait) MXV_HIP(h, hipEventCreateWithFlags(&h->ev_wait, hipEventDisableTiming));
@@ -1598,14 +1451,10 @@ int mxv_wait_stream(mxv_handle *h, void *other_stream) {
 }
 
 int mxv_set_stream(mxv_handle *h, void *stream) {
-    MXV_CHECK_HANDLE(h);
-    if (int rc = use_device(h)) return rc;
-    if (h->stream) MXV_HIP(h, hipStreamSynchronize(h->stream));
-    free_graphs(h);
-    if (h->own_stream && h->stream) MXV_HIP(h, hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return MXV_OK;
+    MXV_CHECK(h);
+    const int rc = set_stream(h, stream);
+    free_graphs(h);  // captured on the old stream
+    return rc;
 }
 
 }  // extern "C"
@@ -1615,16 +1464,16 @@ int mxv_set_stream(mxv_handle *h, void *stream) {
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" int mxv_rollout_mixed(mxv_handle *const *handles, int32_t count, int32_t K, int32_t per_step, const mxv_step_outputs *outs) {
     if (!handles || !outs || count < 1 || count > MXV_MAX_MIXED)
-        return fail(nullptr, MXV_ERR_INVALID_ARG, "mxv_rollout_mixed: 1..%d handles with their outputs", MXV_MAX_MIXED);
+        return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "mxv_rollout_mixed: 1..%d handles with their outputs", MXV_MAX_MIXED);
     mxv_handle *h0 = handles[0];
-    MXV_CHECK_HANDLE(h0);
+    MXV_CHECK(h0);
     if (K < 2) return fail(h0, MXV_ERR_UNSUPPORTED, "mxv_rollout_mixed fuses K >= 2 steps (use mxv_step_sampled per handle for single steps)");
     MixedArgs m{};
     m.count = count;
     uint32_t blocks = 0;
     for (int i = 0; i < count; ++i) {
         mxv_handle *h = handles[i];
-        MXV_CHECK_HANDLE(h);
+        MXV_CHECK(h);
         if (h->cfg.device != h0->cfg.device) return fail(h0, MXV_ERR_INVALID_ARG, "segment %d lives on another device", i);
         for (int j = 0; j < i; ++j)
             if (handles[j] == h) return fail(h0, MXV_ERR_INVALID_ARG, "handle listed twice (segments %d and %d)", j, i);
@@ -1744,17 +1593,17 @@ extern "C" {
 
 int mxv_comm_unique_id(void *id_out) {
     static_assert(sizeof(ncclUniqueId) == MXV_COMM_ID_BYTES, "MXV_COMM_ID_BYTES must be RCCL's unique-id size");
-    if (!id_out) return fail(nullptr, MXV_ERR_INVALID_ARG, "unique-id pointer is NULL");
+    if (!id_out) return fail<mxv_handle>(nullptr, MXV_ERR_INVALID_ARG, "unique-id pointer is NULL");
     RcclApi &api = rccl();
-    if (!api.error.empty()) return fail(nullptr, MXV_ERR_UNSUPPORTED, "%s", api.error.c_str());
+    if (!api.error.empty()) return fail<mxv_handle>(nullptr, MXV_ERR_UNSUPPORTED, "%s", api.error.c_str());
     ncclUniqueId id;
-    MXV_NCCL(nullptr, api.GetUniqueId(&id));
+    MXV_NCCL((mxv_handle *)nullptr, api.GetUniqueId(&id));
     std::memcpy(id_out, &id, sizeof id);
     return MXV_OK;
 }
 
 int mxv_comm_init(mxv_handle *h, int32_t rank, int32_t world, const void *unique_id) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!unique_id || world < 1 || rank < 0 || rank >= world)
         return fail(h, MXV_ERR_INVALID_ARG, "mxv_comm_init: rank %d of %d with id %p", rank, world, unique_id);
     RcclApi &api = rccl();
@@ -1777,7 +1626,7 @@ int mxv_comm_init(mxv_handle *h, int32_t rank, int32_t world, const void *unique
 }
 
 int mxv_comm_destroy(mxv_handle *h) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->comm) return MXV_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
@@ -1799,7 +1648,7 @@ int mxv_comm_destroy(mxv_handle *h) {
 int mxv_allgather_outputs(mxv_handle *h, const float *obs_dev, const void *reward_dev, const uint8_t *terminated_dev,
                           const uint8_t *truncated_dev, float *all_obs_dev, void *all_reward_dev, uint8_t *all_terminated_dev,
                           uint8_t *all_truncated_dev) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!h->comm) return fail(h, MXV_ERR_INVALID_ARG, "mxv_allgather_outputs: call mxv_comm_init first");
     if (int rc = use_device(h)) return rc;
     RcclApi &api = rccl();
@@ -1826,7 +1675,7 @@ int mxv_allgather_outputs(mxv_handle *h, const float *obs_dev, const void *rewar
 }
 
 int mxv_allgather_wait(mxv_handle *h, int32_t age, int32_t host_sync) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (age < 0 || age > 1) return fail(h, MXV_ERR_INVALID_ARG, "mxv_allgather_wait: age must be 0 (last gather) or 1 (the one before)");
     if (h->gathers <= (uint64_t)age) return MXV_OK;  // no such gather yet
     if (int rc = use_device(h)) return rc;
@@ -1839,7 +1688,7 @@ int mxv_allgather_wait(mxv_handle *h, int32_t age, int32_t host_sync) {
 }
 
 int mxv_comm_stream(mxv_handle *h, void **stream) {
-    MXV_CHECK_HANDLE(h);
+    MXV_CHECK(h);
     if (!stream) return fail(h, MXV_ERR_INVALID_ARG, "stream pointer is NULL");
     *stream = (void *)h->comm_stream;
     return MXV_OK;

@@ -17,13 +17,11 @@
 // reference's dtypes (22 B with the contract's 4-byte scalars: mxv_bj_rollout_compact).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <new>
-#include <string>
 
 #include "mxv_device.hpp"
+#include "mxv_host.hpp"
 
 using namespace mxv;
 
@@ -289,9 +287,6 @@ struct BjResetArgs {
     float *ep_acc;        // may be nullptr: zeroed for the envs being reset (record_episode_statistics.py:91-94)
 };
 
-__global__ void bj_set_word_kernel(uint64_t *dst, uint64_t v) { *dst = v; }
-__global__ void bj_add_word_kernel(uint64_t *dst, uint64_t d) { *dst += d; }
-
 __global__ void __launch_bounds__(kBjBlock) bj_reset_kernel(BjResetArgs a) {
     const int64_t e = (int64_t)blockIdx.x * kBjBlock + threadIdx.x;
     if (e >= a.n) return;
@@ -324,21 +319,12 @@ __global__ void __launch_bounds__(kBjBlock) bj_reset_kernel(BjResetArgs a) {
 
 }  // namespace
 
-struct mxv_bj {
+struct mxv_bj : mxv::HostCore {
+    static constexpr const char *kNullMessage = "NULL mxv_bj";
+    mxv_bj() : HostCore("mxv_bj") {}
     mxv_bj_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int32_t *state = nullptr, *elapsed = nullptr, *err = nullptr;
-    uint64_t *seeds = nullptr;
-    uint64_t base_seed = 0, action_seed = 0, t = 0;
-    uint64_t *t_dev = nullptr;   // device clock (mxv_bj_set_device_clock)
-    bool dev_clock = false;
-    uint32_t r = 0;
-    bool was_reset = false;
-    // episode statistics (mxv_bj_episode_stats): running returns, the caller's trajectory outputs, dense staging of host steps
-    float *ep_acc = nullptr, *ep_return_out = nullptr, *st_ep_r = nullptr;
-    int32_t *ep_length_out = nullptr, *st_ep_l = nullptr;
-    bool ep_host_step = false;
+    int32_t *state = nullptr, *elapsed = nullptr;
+    bool ep_host_step = false;   // the launch in flight is a host step: its episode statistics go to the staging arrays
     // staging of the *_host calls
     int64_t *st_actions = nullptr, *st_obs = nullptr, *st_final = nullptr;
     double *st_reward = nullptr;
@@ -348,83 +334,36 @@ struct mxv_bj {
     char *hm_block = nullptr;
     int32_t *hm_err = nullptr;
     bool hostmap = false, err_in_block = false;
-    std::string error;
 };
 
 namespace {
 
-thread_local std::string g_bj_create_error;
-
-int bfail(mxv_bj *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h)
-        h->error = buf;
-    else
-        g_bj_create_error = buf;
-    return code;
+int invalid_action(mxv_bj *h) {
+    return fail(h, MXV_ERR_INVALID_ACTION, "action outside {0, 1} (Discrete(2).contains assert, blackjack.py:122)");
 }
-
-#define BJ_HIP(h, expr)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return bfail((h), MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define BJ_CHECK(h) \
-    if (!(h)) return bfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_bj")
 
 int bj_latched(mxv_bj *h) {
     int32_t e = 0;
-    BJ_HIP(h, hipMemcpyAsync(&e, h->err, sizeof e, hipMemcpyDeviceToHost, h->stream));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    if (e != 0) {
-        BJ_HIP(h, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
-        return bfail(h, MXV_ERR_INVALID_ACTION, "action outside {0, 1} (Discrete(2).contains assert, blackjack.py:122)");
-    }
-    return MXV_OK;
-}
-
-// see mxv_set_device_clock (include/mxv.h): the step index on the device, advanced on the stream
-int bj_clock_add(mxv_bj *h, int64_t delta) {
-    h->t += (uint64_t)delta;
-    if (h->dev_clock) {
-        hipLaunchKernelGGL(bj_add_word_kernel, dim3(1), dim3(1), 0, h->stream, h->t_dev, (uint64_t)delta);
-        BJ_HIP(h, hipGetLastError());
-    }
-    return MXV_OK;
-}
-int bj_clock_set(mxv_bj *h) {
-    if (h->dev_clock) {
-        hipLaunchKernelGGL(bj_set_word_kernel, dim3(1), dim3(1), 0, h->stream, h->t_dev, h->t);
-        BJ_HIP(h, hipGetLastError());
-    }
-    return MXV_OK;
-}
-
-int bj_aligned(mxv_bj *h, const void *p, size_t bytes, const char *what) {   // see check_aligned in mxv_api.cpp
-    if (p && ((uintptr_t)p & (bytes - 1)) != 0) return bfail(h, MXV_ERR_INVALID_ARG, "%s pointer %p is not %zu-byte aligned", what, p, bytes);
-    return MXV_OK;
+    if (int rc = take_latched(h, &e)) return rc;
+    return e != 0 ? invalid_action(h) : MXV_OK;
 }
 
 int bj_launch(mxv_bj *h, int K, int64_t slice, const int64_t *actions, int64_t act_slice, void *actions_out,
               const int8_t *cards, void *obs, void *reward, uint8_t *term, uint8_t *trunc, void *final_obs, int out_mode = 1) {
-    if (!h->was_reset) return bfail(h, MXV_ERR_RESET_NEEDED, "Cannot call step before calling reset (gym.error.ResetNeeded)");
-    if (!obs) return bfail(h, MXV_ERR_INVALID_ARG, "obs pointer is NULL");
-    if (K <= 0) return bfail(h, MXV_ERR_INVALID_ARG, "K must be positive");
-    if (cards && K != 1) return bfail(h, MXV_ERR_INVALID_ARG, "injected cards are per step: K must be 1");
-    if (cards && (!actions || out_mode != 1)) return bfail(h, MXV_ERR_INVALID_ARG, "injected cards need given actions and the reference's dtypes");
+    if (!h->was_reset) return fail(h, MXV_ERR_RESET_NEEDED, "Cannot call step before calling reset (gym.error.ResetNeeded)");
+    if (!obs) return fail(h, MXV_ERR_INVALID_ARG, "obs pointer is NULL");
+    if (K <= 0) return fail(h, MXV_ERR_INVALID_ARG, "K must be positive");
+    if (cards && K != 1) return fail(h, MXV_ERR_INVALID_ARG, "injected cards are per step: K must be 1");
+    if (cards && (!actions || out_mode != 1)) return fail(h, MXV_ERR_INVALID_ARG, "injected cards need given actions and the reference's dtypes");
     {
         const size_t w = out_mode == 1 ? 8 : 4;
         const struct { const void *p; size_t b; const char *what; } t[] = {
             {actions, 8, "actions"}, {actions_out, w, "actions_out"}, {obs, w, "obs"}, {reward, w, "reward"}, {final_obs, w, "final_obs"},
             {h->ep_return_out, 4, "episode return"}, {h->ep_length_out, 4, "episode length"}};
         for (const auto &e : t)
-            if (int rc = bj_aligned(h, e.p, e.b, e.what)) return rc;
+            if (int rc = check_aligned(h, e.p, e.b, e.what)) return rc;
     }
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     BjArgs a{};
     a.state = h->state; a.elapsed = h->elapsed; a.seeds = h->seeds; a.actions = actions; a.actions_out = actions_out;
     a.cards = cards; a.obs = obs; a.reward = reward; a.terminated = term; a.truncated = trunc; a.final_obs = final_obs;
@@ -447,13 +386,13 @@ int bj_launch(mxv_bj *h, int K, int64_t slice, const int64_t *actions, int64_t a
     else if (out_mode == 1) hipLaunchKernelGGL((bj_kernel<false, true, 1>), grid, block, 0, h->stream, a);
     else if (actions) hipLaunchKernelGGL((bj_kernel<false, false, 2>), grid, block, 0, h->stream, a);
     else hipLaunchKernelGGL((bj_kernel<false, true, 2>), grid, block, 0, h->stream, a);
-    BJ_HIP(h, hipGetLastError());
-    return bj_clock_add(h, K);
+    MXV_HIP(h, hipGetLastError());
+    return clock_add(h, K);
 }
 
 int bj_do_reset(mxv_bj *h, const uint8_t *mask_dev, const int8_t *cards_dev, int64_t *obs_dev) {
-    if (int rc = bj_aligned(h, obs_dev, 8, "obs")) return rc;
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
+    if (int rc = check_aligned(h, obs_dev, 8, "obs")) return rc;
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     h->r += 1;
     BjResetArgs a{};
     a.state = h->state; a.elapsed = h->elapsed; a.seeds = h->seeds; a.mask = mask_dev; a.cards = cards_dev; a.obs = obs_dev;
@@ -461,7 +400,7 @@ int bj_do_reset(mxv_bj *h, const uint8_t *mask_dev, const int8_t *cards_dev, int
     a.ep_acc = h->ep_acc;
     const unsigned blocks = (unsigned)((h->cfg.num_envs + kBjBlock - 1) / kBjBlock);
     hipLaunchKernelGGL(bj_reset_kernel, dim3(blocks), dim3(kBjBlock), 0, h->stream, a);
-    BJ_HIP(h, hipGetLastError());
+    MXV_HIP(h, hipGetLastError());
     h->was_reset = true;
     return MXV_OK;
 }
@@ -473,7 +412,7 @@ int bj_staging(mxv_bj *h) {
         auto up = [](size_t b) { return (b + 255) / 256 * 256; };
         const size_t b8 = up(n * 8), b24 = up(3 * n * 8), b1 = up(n), bc = up(n * MXV_BJ_MAX_DRAWS), total = 2 * b8 + 2 * b24 + 2 * b1 + bc + 256;
         if (total <= (size_t)2 << 20) {
-            BJ_HIP(h, hipHostMalloc((void **)&h->hm_block, total, hipHostMallocDefault));
+            MXV_HIP(h, hipHostMalloc((void **)&h->hm_block, total, hipHostMallocDefault));
             char *p = h->hm_block;
             h->st_actions = (int64_t *)p; p += b8;
             h->st_obs = (int64_t *)p; p += b24;
@@ -488,13 +427,13 @@ int bj_staging(mxv_bj *h) {
             return MXV_OK;
         }
     }
-    BJ_HIP(h, hipMalloc((void **)&h->st_actions, n * 8));
-    BJ_HIP(h, hipMalloc((void **)&h->st_obs, 3 * n * 8));
-    BJ_HIP(h, hipMalloc((void **)&h->st_final, 3 * n * 8));
-    BJ_HIP(h, hipMalloc((void **)&h->st_reward, n * 8));
-    BJ_HIP(h, hipMalloc((void **)&h->st_term, n));
-    BJ_HIP(h, hipMalloc((void **)&h->st_trunc, n));
-    BJ_HIP(h, hipMalloc((void **)&h->st_cards, n * MXV_BJ_MAX_DRAWS));
+    MXV_HIP(h, hipMalloc((void **)&h->st_actions, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_obs, 3 * n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_final, 3 * n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_reward, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_term, n));
+    MXV_HIP(h, hipMalloc((void **)&h->st_trunc, n));
+    MXV_HIP(h, hipMalloc((void **)&h->st_cards, n * MXV_BJ_MAX_DRAWS));
     return MXV_OK;
 }
 
@@ -503,21 +442,23 @@ int bj_staging(mxv_bj *h) {
 extern "C" {
 
 int mxv_bj_create(const mxv_bj_config *cfg, mxv_bj **out) {
-    if (!cfg || !out) return bfail(nullptr, MXV_ERR_INVALID_ARG, "NULL config or output pointer");
+    if (!cfg || !out) return fail<mxv_bj>(nullptr, MXV_ERR_INVALID_ARG, "NULL config or output pointer");
     *out = nullptr;
     if (cfg->num_envs <= 0 || cfg->num_envs > ((int64_t)1 << 28))
-        return bfail(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be in [1, 2^28] (one handle; shard larger batches over handles: env_offset)");
+        return fail<mxv_bj>(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be in [1, 2^28] (one handle; shard larger batches over handles: env_offset)");
     if (cfg->env_offset < 0 || cfg->env_offset % MXV_ENV_ALIGN != 0)
-        return bfail(nullptr, MXV_ERR_INVALID_ARG, "env_offset must be a non-negative multiple of %d", MXV_ENV_ALIGN);
+        return fail<mxv_bj>(nullptr, MXV_ERR_INVALID_ARG, "env_offset must be a non-negative multiple of %d", MXV_ENV_ALIGN);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
-        return bfail(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
+        return fail<mxv_bj>(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
                      e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (cfg->device < 0 || cfg->device >= ndev) return bfail(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", cfg->device);
+    if (cfg->device < 0 || cfg->device >= ndev) return fail<mxv_bj>(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", cfg->device);
     mxv_bj *h = new (std::nothrow) mxv_bj();
-    if (!h) return bfail(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
+    if (!h) return fail<mxv_bj>(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
     h->cfg = *cfg;
+    h->device = cfg->device;
+    h->num_envs = cfg->num_envs;
     h->base_seed = cfg->seed;
     h->action_seed = cfg->action_seed;
     const size_t n = (size_t)cfg->num_envs;
@@ -534,7 +475,7 @@ int mxv_bj_create(const mxv_bj_config *cfg, mxv_bj **out) {
     if (err == hipSuccess) err = hipMemsetAsync(h->t_dev, 0, 8, h->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(h->stream);
     if (err != hipSuccess) {
-        bfail(nullptr, MXV_ERR_HIP, "mxv_bj_create: %s", hipGetErrorString(err));
+        fail<mxv_bj>(nullptr, MXV_ERR_HIP, "mxv_bj_create: %s", hipGetErrorString(err));
         mxv_bj_destroy(h);
         return MXV_ERR_HIP;
     }
@@ -544,11 +485,7 @@ int mxv_bj_create(const mxv_bj_config *cfg, mxv_bj **out) {
 
 int mxv_bj_destroy(mxv_bj *h) {
     if (!h) return MXV_OK;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *bufs[] = {h->state, h->elapsed, h->err, h->seeds, h->t_dev, h->ep_acc, h->st_ep_r, h->st_ep_l};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
+    drain(h);
     if (h->hostmap) {
         (void)hipHostFree(h->hm_block);
     } else {
@@ -556,48 +493,34 @@ int mxv_bj_destroy(mxv_bj *h) {
         for (void *p : stage)
             if (p) (void)hipFree(p);
     }
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    free_core(h, {h->state, h->elapsed});
     delete h;
     return MXV_OK;
 }
 
-const char *mxv_bj_last_error(const mxv_bj *h) { return h ? h->error.c_str() : g_bj_create_error.c_str(); }
+const char *mxv_bj_last_error(const mxv_bj *h) { return last_error(h); }
 
 int mxv_bj_seed(mxv_bj *h, uint64_t base_seed, const uint64_t *per_env_seeds_host, uint64_t action_seed) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    h->base_seed = base_seed;
+    MXV_CHECK(h);
     h->action_seed = action_seed;
-    h->t = 0;
-    h->r = 0;
-    if (int rc = bj_clock_set(h)) return rc;
-    if (per_env_seeds_host) {
-        const size_t bytes = (size_t)h->cfg.num_envs * sizeof(uint64_t);
-        if (!h->seeds) BJ_HIP(h, hipMalloc((void **)&h->seeds, bytes));
-        BJ_HIP(h, hipMemcpy(h->seeds, per_env_seeds_host, bytes, hipMemcpyHostToDevice));
-    } else if (h->seeds) {
-        BJ_HIP(h, hipFree(h->seeds));
-        h->seeds = nullptr;
-    }
-    return MXV_OK;
+    return reseed(h, base_seed, per_env_seeds_host);
 }
 
 int mxv_bj_reset(mxv_bj *h, const uint8_t *mask_dev, const int8_t *cards_dev, int64_t *obs_dev) {
-    BJ_CHECK(h);
+    MXV_CHECK(h);
     return bj_do_reset(h, mask_dev, cards_dev, obs_dev);
 }
 
 int mxv_bj_step(mxv_bj *h, const int64_t *actions_dev, const int8_t *cards_dev, int64_t *obs_dev, double *reward_dev,
                 uint8_t *terminated_dev, uint8_t *truncated_dev, int64_t *final_obs_dev) {
-    BJ_CHECK(h);
-    if (!actions_dev) return bfail(h, MXV_ERR_INVALID_ARG, "actions pointer is NULL (use mxv_bj_rollout for sampled actions)");
+    MXV_CHECK(h);
+    if (!actions_dev) return fail(h, MXV_ERR_INVALID_ARG, "actions pointer is NULL (use mxv_bj_rollout for sampled actions)");
     return bj_launch(h, 1, 0, actions_dev, 0, nullptr, cards_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, final_obs_dev);
 }
 
 int mxv_bj_rollout(mxv_bj *h, int32_t K, int32_t per_step, const int64_t *actions_tape_dev, int64_t *actions_out_dev,
                    int64_t *obs_dev, double *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, int64_t *final_obs_dev) {
-    BJ_CHECK(h);
+    MXV_CHECK(h);
     return bj_launch(h, K, per_step ? h->cfg.num_envs : 0, actions_tape_dev, actions_tape_dev ? h->cfg.num_envs : 0,
                      actions_tape_dev ? nullptr : actions_out_dev, nullptr, obs_dev, reward_dev, terminated_dev, truncated_dev,
                      final_obs_dev);
@@ -605,41 +528,41 @@ int mxv_bj_rollout(mxv_bj *h, int32_t K, int32_t per_step, const int64_t *action
 
 int mxv_bj_rollout_compact(mxv_bj *h, int32_t K, int32_t per_step, const int64_t *actions_tape_dev, int32_t *actions_out_dev,
                            int32_t *obs_dev, float *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, int32_t *final_obs_dev) {
-    BJ_CHECK(h);
+    MXV_CHECK(h);
     return bj_launch(h, K, per_step ? h->cfg.num_envs : 0, actions_tape_dev, actions_tape_dev ? h->cfg.num_envs : 0,
                      actions_tape_dev ? nullptr : actions_out_dev, nullptr, obs_dev, reward_dev, terminated_dev, truncated_dev,
                      final_obs_dev, 2);
 }
 
 int mxv_bj_reset_host(mxv_bj *h, const int8_t *cards_host, int64_t *obs_host) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_CHECK(h);
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = bj_staging(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
     if (h->hostmap) {
         if (cards_host) std::memcpy(h->st_cards, cards_host, n * 4);
         if (int rc = bj_do_reset(h, nullptr, cards_host ? h->st_cards : nullptr, obs_host ? h->st_obs : nullptr)) return rc;
-        BJ_HIP(h, hipStreamSynchronize(h->stream));
+        MXV_HIP(h, hipStreamSynchronize(h->stream));
         if (obs_host) std::memcpy(obs_host, h->st_obs, 3 * n * 8);
         return MXV_OK;
     }
-    if (cards_host) BJ_HIP(h, hipMemcpyAsync(h->st_cards, cards_host, n * 4, hipMemcpyHostToDevice, h->stream));
+    if (cards_host) MXV_HIP(h, hipMemcpyAsync(h->st_cards, cards_host, n * 4, hipMemcpyHostToDevice, h->stream));
     if (int rc = bj_do_reset(h, nullptr, cards_host ? h->st_cards : nullptr, obs_host ? h->st_obs : nullptr)) return rc;
-    if (obs_host) BJ_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
+    if (obs_host) MXV_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
+    MXV_HIP(h, hipStreamSynchronize(h->stream));
     return MXV_OK;
 }
 
 int mxv_bj_step_host(mxv_bj *h, const int64_t *actions_host, const int8_t *cards_host, int64_t *obs_host, double *reward_host,
                      uint8_t *terminated_host, uint8_t *truncated_host, int64_t *final_obs_host) {
-    BJ_CHECK(h);
-    if (!actions_host || !obs_host) return bfail(h, MXV_ERR_INVALID_ARG, "actions/obs pointer is NULL");
+    MXV_CHECK(h);
+    if (!actions_host || !obs_host) return fail(h, MXV_ERR_INVALID_ARG, "actions/obs pointer is NULL");
     if (cards_host)   // an injected deck: card values (1 = ace ... 10, blackjack.py:14), 0 = padding behind the draws a step consumes
         for (size_t i = 0; i < (size_t)h->cfg.num_envs * MXV_BJ_MAX_DRAWS; ++i)
             if (cards_host[i] < 0 || cards_host[i] > 10)
-                return bfail(h, MXV_ERR_INVALID_ARG, "injected card %d at [%zu][%zu] is no card value (1..10; 0 pads)", (int)cards_host[i],
+                return fail(h, MXV_ERR_INVALID_ARG, "injected card %d at [%zu][%zu] is no card value (1..10; 0 pads)", (int)cards_host[i],
                              i / MXV_BJ_MAX_DRAWS, i % MXV_BJ_MAX_DRAWS);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = bj_staging(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
     if (h->hostmap) {   // one launch + one synchronisation: the kernel reads and writes the pinned block itself
@@ -652,7 +575,7 @@ int mxv_bj_step_host(mxv_bj *h, const int64_t *actions_host, const int8_t *cards
         h->err_in_block = false;
         h->ep_host_step = false;
         if (lrc) return lrc;
-        BJ_HIP(h, hipStreamSynchronize(h->stream));
+        MXV_HIP(h, hipStreamSynchronize(h->stream));
         std::memcpy(obs_host, h->st_obs, 3 * n * 8);
         if (reward_host) std::memcpy(reward_host, h->st_reward, n * 8);
         if (terminated_host) std::memcpy(terminated_host, h->st_term, n);
@@ -660,147 +583,81 @@ int mxv_bj_step_host(mxv_bj *h, const int64_t *actions_host, const int8_t *cards
         if (final_obs_host) std::memcpy(final_obs_host, h->st_final, 3 * n * 8);
         if (*h->hm_err != 0) {
             *h->hm_err = 0;
-            (void)bj_clock_add(h, -1);
-            return bfail(h, MXV_ERR_INVALID_ACTION, "action outside {0, 1} (Discrete(2).contains assert, blackjack.py:122)");
+            (void)clock_add(h, -1);
+            return invalid_action(h);
         }
         return MXV_OK;
     }
-    BJ_HIP(h, hipMemcpyAsync(h->st_actions, actions_host, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (cards_host) BJ_HIP(h, hipMemcpyAsync(h->st_cards, cards_host, n * MXV_BJ_MAX_DRAWS, hipMemcpyHostToDevice, h->stream));
+    MXV_HIP(h, hipMemcpyAsync(h->st_actions, actions_host, n * 8, hipMemcpyHostToDevice, h->stream));
+    if (cards_host) MXV_HIP(h, hipMemcpyAsync(h->st_cards, cards_host, n * MXV_BJ_MAX_DRAWS, hipMemcpyHostToDevice, h->stream));
     h->ep_host_step = true;
     const int lrc = bj_launch(h, 1, 0, h->st_actions, 0, nullptr, cards_host ? h->st_cards : nullptr, h->st_obs, h->st_reward,
                               h->st_term, h->st_trunc, final_obs_host ? h->st_final : nullptr);
     h->ep_host_step = false;
     if (lrc) return lrc;
-    BJ_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (reward_host) BJ_HIP(h, hipMemcpyAsync(reward_host, h->st_reward, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (terminated_host) BJ_HIP(h, hipMemcpyAsync(terminated_host, h->st_term, n, hipMemcpyDeviceToHost, h->stream));
-    if (truncated_host) BJ_HIP(h, hipMemcpyAsync(truncated_host, h->st_trunc, n, hipMemcpyDeviceToHost, h->stream));
-    if (final_obs_host) BJ_HIP(h, hipMemcpyAsync(final_obs_host, h->st_final, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
+    MXV_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (reward_host) MXV_HIP(h, hipMemcpyAsync(reward_host, h->st_reward, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (terminated_host) MXV_HIP(h, hipMemcpyAsync(terminated_host, h->st_term, n, hipMemcpyDeviceToHost, h->stream));
+    if (truncated_host) MXV_HIP(h, hipMemcpyAsync(truncated_host, h->st_trunc, n, hipMemcpyDeviceToHost, h->stream));
+    if (final_obs_host) MXV_HIP(h, hipMemcpyAsync(final_obs_host, h->st_final, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
     int rc = bj_latched(h);
-    if (rc == MXV_ERR_INVALID_ACTION) (void)bj_clock_add(h, -1);
+    if (rc == MXV_ERR_INVALID_ACTION) (void)clock_add(h, -1);
     return rc;
 }
 
 /* gym.wrappers.RecordEpisodeStatistics fused into the step (record_episode_statistics.py:96-151): see mxv_toytext.h */
 int mxv_bj_episode_stats(mxv_bj *h, int32_t enable) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (enable && !h->ep_acc) {
-        BJ_HIP(h, hipMalloc((void **)&h->ep_acc, n * sizeof(float)));
-        BJ_HIP(h, hipMalloc((void **)&h->st_ep_r, n * sizeof(float)));
-        BJ_HIP(h, hipMalloc((void **)&h->st_ep_l, n * sizeof(int32_t)));
-        BJ_HIP(h, hipMemsetAsync(h->ep_acc, 0, n * sizeof(float), h->stream));
-        BJ_HIP(h, hipMemsetAsync(h->st_ep_r, 0, n * sizeof(float), h->stream));
-        BJ_HIP(h, hipMemsetAsync(h->st_ep_l, 0, n * sizeof(int32_t), h->stream));
-        BJ_HIP(h, hipStreamSynchronize(h->stream));
-    } else if (!enable && h->ep_acc) {
-        BJ_HIP(h, hipFree(h->ep_acc));
-        BJ_HIP(h, hipFree(h->st_ep_r));
-        BJ_HIP(h, hipFree(h->st_ep_l));
-        h->ep_acc = h->st_ep_r = nullptr;
-        h->st_ep_l = nullptr;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return episode_stats(h, enable);
 }
 
 int mxv_bj_set_episode_outputs(mxv_bj *h, float *ep_return_dev, int32_t *ep_length_dev) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    h->ep_return_out = ep_return_dev;
-    h->ep_length_out = ep_length_dev;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_episode_outputs(h, ep_return_dev, ep_length_dev);
 }
 
 int mxv_bj_episode_stats_host(mxv_bj *h, float *ep_return_host, int32_t *ep_length_host, float *running_return_host) {
-    BJ_CHECK(h);
-    if (!h->ep_acc) return bfail(h, MXV_ERR_INVALID_ARG, "episode statistics are not enabled (mxv_bj_episode_stats)");
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (ep_return_host) BJ_HIP(h, hipMemcpyAsync(ep_return_host, h->st_ep_r, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (ep_length_host) BJ_HIP(h, hipMemcpyAsync(ep_length_host, h->st_ep_l, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (running_return_host) BJ_HIP(h, hipMemcpyAsync(running_return_host, h->ep_acc, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return episode_stats_host(h, ep_return_host, ep_length_host, running_return_host);
 }
 
 int mxv_bj_set_running_returns(mxv_bj *h, const float *running_return_host) {
-    BJ_CHECK(h);
-    if (!h->ep_acc) return bfail(h, MXV_ERR_INVALID_ARG, "episode statistics are not enabled (mxv_bj_episode_stats)");
-    if (!running_return_host) return bfail(h, MXV_ERR_INVALID_ARG, "NULL pointer");
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    BJ_HIP(h, hipMemcpyAsync(h->ep_acc, running_return_host, (size_t)h->cfg.num_envs * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_running_returns(h, running_return_host);
 }
 
 int mxv_bj_get_state(mxv_bj *h, int32_t *state_host, int32_t *elapsed_host) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (state_host) BJ_HIP(h, hipMemcpyAsync(state_host, h->state, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (elapsed_host) BJ_HIP(h, hipMemcpyAsync(elapsed_host, h->elapsed, n * 4, hipMemcpyDeviceToHost, h->stream));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return read_state32(h, h->state, h->elapsed, state_host, elapsed_host);
 }
 
 int mxv_bj_get_counters(mxv_bj *h, uint64_t *t, uint32_t *r) {
-    BJ_CHECK(h);
-    if (h->dev_clock) {
-        BJ_HIP(h, hipSetDevice(h->cfg.device));
-        BJ_HIP(h, hipMemcpyAsync(&h->t, h->t_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        BJ_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (t) *t = h->t;
-    if (r) *r = h->r;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return get_counters(h, t, r);
 }
 
 int mxv_bj_set_state(mxv_bj *h, const int32_t *state_host, const int32_t *elapsed_host, uint64_t t, uint32_t r) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (state_host) BJ_HIP(h, hipMemcpyAsync(h->state, state_host, n * 4, hipMemcpyHostToDevice, h->stream));
-    if (elapsed_host) BJ_HIP(h, hipMemcpyAsync(h->elapsed, elapsed_host, n * 4, hipMemcpyHostToDevice, h->stream));
-    BJ_HIP(h, hipStreamSynchronize(h->stream));
+    MXV_CHECK(h);
+    if (int rc = write_state32(h, h->state, h->elapsed, state_host, elapsed_host)) return rc;
     h->t = t;
     h->r = r;
-    h->was_reset = true;
-    return bj_clock_set(h);
+    return clock_set(h);
 }
 
 int mxv_bj_set_device_clock(mxv_bj *h, int32_t on) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    if (on && !h->dev_clock) {
-        h->dev_clock = true;
-        return bj_clock_set(h);
-    }
-    if (!on && h->dev_clock) {
-        BJ_HIP(h, hipMemcpyAsync(&h->t, h->t_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        BJ_HIP(h, hipStreamSynchronize(h->stream));
-        h->dev_clock = false;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_device_clock(h, on);
 }
 
 int mxv_bj_sync(mxv_bj *h) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_CHECK(h);
+    if (int rc = use_device(h)) return rc;
     return bj_latched(h);
 }
 
 int mxv_bj_set_stream(mxv_bj *h, void *stream) {
-    BJ_CHECK(h);
-    BJ_HIP(h, hipSetDevice(h->cfg.device));
-    if (h->stream) BJ_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->own_stream && h->stream) BJ_HIP(h, hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_stream(h, stream);
 }
 
 }  // extern "C"

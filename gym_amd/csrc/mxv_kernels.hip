@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "mxv_host.hpp"
 #include "mxv_kernels.hpp"
 
 namespace mxv {

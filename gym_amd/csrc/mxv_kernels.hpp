@@ -153,7 +153,5 @@ hipError_t launch_compact_final(int obs_dim, const CompactArgs &a, hipStream_t s
 hipError_t launch_write_probe(float *obs, double *rew, int64_t *act, uint8_t *term, uint8_t *trunc, int64_t n, int K, hipStream_t stream);
 hipError_t launch_write_probe_env(int env_id, int flags, float *obs, void *rew, void *act, uint8_t *term, uint8_t *trunc, int64_t n, int K,
                                   hipStream_t stream);
-hipError_t launch_set_word(uint64_t *dst, uint64_t value, hipStream_t stream);
-hipError_t launch_add_word(uint64_t *dst, uint64_t delta, hipStream_t stream);   // *dst += delta (two's complement: a negative delta subtracts)
 
 }  // namespace mxv

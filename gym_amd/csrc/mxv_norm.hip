@@ -27,14 +27,17 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdarg>
-#include <cstdio>
 #include <new>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/mxv.h"
+#include "mxv_host.hpp"
+
+using mxv::check_aligned;
+using mxv::fail;
+using mxv::last_error;
 
 namespace {
 
@@ -410,6 +413,7 @@ __global__ void __launch_bounds__(kThreads) reward_apply_kernel(const RT *__rest
 }  // namespace
 
 struct mxv_norm {
+    static constexpr const char *kNullMessage = "NULL mxv_norm";
     int device = 0, dim = 0;
     int64_t n = 0;
     hipStream_t stream = nullptr;
@@ -425,27 +429,6 @@ struct mxv_norm {
 
 namespace {
 
-thread_local std::string g_norm_create_error;
-
-int nfail(mxv_norm *nm, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (nm)
-        nm->error = buf;
-    else
-        g_norm_create_error = buf;
-    return code;
-}
-
-#define NRM_HIP(nm, expr)                                                                               \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return nfail((nm), MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 bool dim_supported(int d) { return d == 1 || d == 2 || d == 3 || d == 4 || d == 6; }
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -453,21 +436,21 @@ int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 int ensure_capacity(mxv_norm *nm, int K, int64_t leaves, int V) {
     const size_t need = (size_t)K * (size_t)leaves * (size_t)V;
     if (need > nm->part_cap) {
-        NRM_HIP(nm, hipStreamSynchronize(nm->stream));
-        if (nm->part_a) NRM_HIP(nm, hipFree(nm->part_a));
-        if (nm->part_b) NRM_HIP(nm, hipFree(nm->part_b));
+        MXV_HIP(nm, hipStreamSynchronize(nm->stream));
+        if (nm->part_a) MXV_HIP(nm, hipFree(nm->part_a));
+        if (nm->part_b) MXV_HIP(nm, hipFree(nm->part_b));
         nm->part_a = nm->part_b = nullptr;
-        NRM_HIP(nm, hipMalloc((void **)&nm->part_a, need * sizeof(double)));
-        NRM_HIP(nm, hipMalloc((void **)&nm->part_b, need * sizeof(double)));
+        MXV_HIP(nm, hipMalloc((void **)&nm->part_a, need * sizeof(double)));
+        MXV_HIP(nm, hipMalloc((void **)&nm->part_b, need * sizeof(double)));
         nm->part_cap = need;
     }
     if ((size_t)K > nm->k_cap) {
-        NRM_HIP(nm, hipStreamSynchronize(nm->stream));
-        if (nm->sums) NRM_HIP(nm, hipFree(nm->sums));
-        if (nm->coef) NRM_HIP(nm, hipFree(nm->coef));
+        MXV_HIP(nm, hipStreamSynchronize(nm->stream));
+        if (nm->sums) MXV_HIP(nm, hipFree(nm->sums));
+        if (nm->coef) MXV_HIP(nm, hipFree(nm->coef));
         nm->sums = nm->coef = nullptr;
-        NRM_HIP(nm, hipMalloc((void **)&nm->sums, (size_t)K * 2 * nm->dim * sizeof(double)));
-        NRM_HIP(nm, hipMalloc((void **)&nm->coef, (size_t)K * 2 * nm->dim * sizeof(double)));
+        MXV_HIP(nm, hipMalloc((void **)&nm->sums, (size_t)K * 2 * nm->dim * sizeof(double)));
+        MXV_HIP(nm, hipMalloc((void **)&nm->coef, (size_t)K * 2 * nm->dim * sizeof(double)));
         nm->k_cap = (size_t)K;
     }
     return MXV_OK;
@@ -481,7 +464,7 @@ int run_tree(mxv_norm *nm, int K, int64_t leaves, int V, double *dst, const doub
         const int64_t groups = ceil_div(leaves, kTreeFan);
         double *target = groups == 1 ? dst : out;
         hipLaunchKernelGGL(tree_kernel, dim3((unsigned)groups, (unsigned)K), dim3(kThreads), 0, nm->stream, in, target, leaves, V);
-        NRM_HIP(nm, hipGetLastError());
+        MXV_HIP(nm, hipGetLastError());
         if (groups == 1) break;
         leaves = groups;
         in = out;
@@ -494,7 +477,7 @@ template <int O>
 int launch_obs_sums(mxv_norm *nm, int K, const float *x, int64_t leaves) {
     hipLaunchKernelGGL(obs_sums_kernel<O>, dim3((unsigned)leaves, (unsigned)K), dim3(kThreads), 0, nm->stream, x, nm->n,
                        leaves, nm->part_a);
-    NRM_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return MXV_OK;
 }
 
@@ -505,7 +488,7 @@ int launch_obs_apply(mxv_norm *nm, int K, const float *x, void *y, int out_f32) 
         hipLaunchKernelGGL((obs_apply_kernel<O, float>), grid, dim3(kThreads), 0, nm->stream, x, (float *)y, nm->coef, nm->n);
     else
         hipLaunchKernelGGL((obs_apply_kernel<O, double>), grid, dim3(kThreads), 0, nm->stream, x, (double *)y, nm->coef, nm->n);
-    NRM_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return MXV_OK;
 }
 
@@ -516,33 +499,29 @@ int launch_obs_apply(mxv_norm *nm, int K, const float *x, void *y, int out_f32) 
         case 3: return fn<3>(__VA_ARGS__);                                          \
         case 4: return fn<4>(__VA_ARGS__);                                          \
         case 6: return fn<6>(__VA_ARGS__);                                          \
-        default: return nfail((nm), MXV_ERR_UNSUPPORTED, "dim %d", (nm)->dim);      \
+        default: return fail((nm), MXV_ERR_UNSUPPORTED, "dim %d", (nm)->dim);      \
     }
 
 int dispatch_obs_sums(mxv_norm *nm, int K, const float *x, int64_t leaves) { DISPATCH_DIM(nm, launch_obs_sums, nm, K, x, leaves) }
 int dispatch_obs_apply(mxv_norm *nm, int K, const float *x, void *y, int out_f32) { DISPATCH_DIM(nm, launch_obs_apply, nm, K, x, y, out_f32) }
 
 int checks(mxv_norm *nm, int K) {
-    if (!nm) return nfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_norm");
-    if (K <= 0) return nfail(nm, MXV_ERR_INVALID_ARG, "K must be positive");
-    if (K > 65535) return nfail(nm, MXV_ERR_INVALID_ARG, "K must be <= 65535 batches per call (grid.y)");
-    NRM_HIP(nm, hipSetDevice(nm->device));
+    MXV_CHECK(nm);
+    if (K <= 0) return fail(nm, MXV_ERR_INVALID_ARG, "K must be positive");
+    if (K > 65535) return fail(nm, MXV_ERR_INVALID_ARG, "K must be <= 65535 batches per call (grid.y)");
+    MXV_HIP(nm, hipSetDevice(nm->device));
     return MXV_OK;
 }
 
-// caller-owned tensors on their element's natural boundary (observation rows: the vector width the kernels load them with)
-int norm_aligned(mxv_norm *nm, const void *p, size_t bytes, const char *what) {
-    if (p && ((uintptr_t)p & (bytes - 1)) != 0) return nfail(nm, MXV_ERR_INVALID_ARG, "%s pointer %p is not %zu-byte aligned", what, p, bytes);
-    return MXV_OK;
-}
+// observation rows on the vector width the kernels load them with (check_aligned)
 size_t row_align(int dim, size_t elem) { return dim % 4 == 0 ? 4 * elem > 16 ? 16 : 4 * elem : (dim % 2 == 0 ? 2 * elem : elem); }
 
 int run_scan(mxv_norm *nm, int K, const double *all_sums, int world, int64_t total_rows, double epsilon, int obs) {
-    if (world < 1 || world > kMaxWorld) return nfail(nm, MXV_ERR_INVALID_ARG, "world must be in [1, %d]", kMaxWorld);
-    if (total_rows <= 0) return nfail(nm, MXV_ERR_INVALID_ARG, "total_rows must be positive");
+    if (world < 1 || world > kMaxWorld) return fail(nm, MXV_ERR_INVALID_ARG, "world must be in [1, %d]", kMaxWorld);
+    if (total_rows <= 0) return fail(nm, MXV_ERR_INVALID_ARG, "total_rows must be positive");
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, nm->stream, all_sums, world, K, nm->dim, (double)total_rows, epsilon,
                        obs, nm->stat, nm->coef);
-    NRM_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return MXV_OK;
 }
 
@@ -551,18 +530,18 @@ int run_scan(mxv_norm *nm, int K, const double *all_sums, int world, int64_t tot
 extern "C" {
 
 int mxv_norm_create(int32_t device, int32_t dim, int64_t num_envs, void *stream, mxv_norm **out) {
-    if (!out) return nfail(nullptr, MXV_ERR_INVALID_ARG, "NULL output pointer");
+    if (!out) return fail<mxv_norm>(nullptr, MXV_ERR_INVALID_ARG, "NULL output pointer");
     *out = nullptr;
-    if (!dim_supported(dim)) return nfail(nullptr, MXV_ERR_UNSUPPORTED, "dim must be one of 1, 2, 3, 4, 6 (got %d)", dim);
-    if (num_envs <= 0) return nfail(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be positive");
+    if (!dim_supported(dim)) return fail<mxv_norm>(nullptr, MXV_ERR_UNSUPPORTED, "dim must be one of 1, 2, 3, 4, 6 (got %d)", dim);
+    if (num_envs <= 0) return fail<mxv_norm>(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be positive");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
-        return nfail(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
+        return fail<mxv_norm>(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
                      e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (device < 0 || device >= ndev) return nfail(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", device);
+    if (device < 0 || device >= ndev) return fail<mxv_norm>(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", device);
     mxv_norm *nm = new (std::nothrow) mxv_norm();
-    if (!nm) return nfail(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
+    if (!nm) return fail<mxv_norm>(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
     nm->device = device;
     nm->dim = dim;
     nm->n = num_envs;
@@ -576,7 +555,7 @@ int mxv_norm_create(int32_t device, int32_t dim, int64_t num_envs, void *stream,
     if (err == hipSuccess) err = hipMemcpy(nm->stat, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMemset(nm->returns, 0, (size_t)num_envs * sizeof(double));  // np.zeros(num_envs), :123
     if (err != hipSuccess) {
-        nfail(nullptr, MXV_ERR_HIP, "mxv_norm_create: %s", hipGetErrorString(err));
+        fail<mxv_norm>(nullptr, MXV_ERR_HIP, "mxv_norm_create: %s", hipGetErrorString(err));
         mxv_norm_destroy(nm);
         return MXV_ERR_HIP;
     }
@@ -595,24 +574,24 @@ int mxv_norm_destroy(mxv_norm *nm) {
     return MXV_OK;
 }
 
-const char *mxv_norm_last_error(const mxv_norm *nm) { return nm ? nm->error.c_str() : g_norm_create_error.c_str(); }
+const char *mxv_norm_last_error(const mxv_norm *nm) { return last_error(nm); }
 
 int mxv_norm_set_stream(mxv_norm *nm, void *stream) {
-    if (!nm) return nfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_norm");
-    NRM_HIP(nm, hipSetDevice(nm->device));
-    NRM_HIP(nm, hipStreamSynchronize(nm->stream));
+    MXV_CHECK(nm);
+    MXV_HIP(nm, hipSetDevice(nm->device));
+    MXV_HIP(nm, hipStreamSynchronize(nm->stream));
     nm->stream = (hipStream_t)stream;
     return MXV_OK;
 }
 
 int mxv_norm_get_state(mxv_norm *nm, double *mean_host, double *var_host, double *count_host, double *returns_host) {
-    if (!nm) return nfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_norm");
-    NRM_HIP(nm, hipSetDevice(nm->device));
+    MXV_CHECK(nm);
+    MXV_HIP(nm, hipSetDevice(nm->device));
     std::vector<double> st(2 * nm->dim + 1);
-    NRM_HIP(nm, hipMemcpyAsync(st.data(), nm->stat, st.size() * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
+    MXV_HIP(nm, hipMemcpyAsync(st.data(), nm->stat, st.size() * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
     if (returns_host)
-        NRM_HIP(nm, hipMemcpyAsync(returns_host, nm->returns, (size_t)nm->n * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
-    NRM_HIP(nm, hipStreamSynchronize(nm->stream));
+        MXV_HIP(nm, hipMemcpyAsync(returns_host, nm->returns, (size_t)nm->n * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
+    MXV_HIP(nm, hipStreamSynchronize(nm->stream));
     for (int j = 0; j < nm->dim; ++j) {
         if (mean_host) mean_host[j] = st[j];
         if (var_host) var_host[j] = st[nm->dim + j];
@@ -622,27 +601,27 @@ int mxv_norm_get_state(mxv_norm *nm, double *mean_host, double *var_host, double
 }
 
 int mxv_norm_set_state(mxv_norm *nm, const double *mean_host, const double *var_host, double count, const double *returns_host) {
-    if (!nm) return nfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_norm");
-    if (!mean_host || !var_host) return nfail(nm, MXV_ERR_INVALID_ARG, "mean/var pointer is NULL");
-    NRM_HIP(nm, hipSetDevice(nm->device));
+    MXV_CHECK(nm);
+    if (!mean_host || !var_host) return fail(nm, MXV_ERR_INVALID_ARG, "mean/var pointer is NULL");
+    MXV_HIP(nm, hipSetDevice(nm->device));
     std::vector<double> st(2 * nm->dim + 1);
     for (int j = 0; j < nm->dim; ++j) {
         st[j] = mean_host[j];
         st[nm->dim + j] = var_host[j];
     }
     st[2 * nm->dim] = count;
-    NRM_HIP(nm, hipMemcpyAsync(nm->stat, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, nm->stream));
+    MXV_HIP(nm, hipMemcpyAsync(nm->stat, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, nm->stream));
     if (returns_host)
-        NRM_HIP(nm, hipMemcpyAsync(nm->returns, returns_host, (size_t)nm->n * sizeof(double), hipMemcpyHostToDevice, nm->stream));
-    NRM_HIP(nm, hipStreamSynchronize(nm->stream));
+        MXV_HIP(nm, hipMemcpyAsync(nm->returns, returns_host, (size_t)nm->n * sizeof(double), hipMemcpyHostToDevice, nm->stream));
+    MXV_HIP(nm, hipStreamSynchronize(nm->stream));
     return MXV_OK;
 }
 
 int mxv_norm_obs_sums(mxv_norm *nm, int32_t K, const float *x_dev, double *sums_dev) {
     if (int rc = checks(nm, K)) return rc;
-    if (!x_dev || !sums_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "x/sums pointer is NULL");
-    if (int rc = norm_aligned(nm, x_dev, row_align(nm->dim, 4), "x")) return rc;
-    if (int rc = norm_aligned(nm, sums_dev, 8, "sums")) return rc;
+    if (!x_dev || !sums_dev) return fail(nm, MXV_ERR_INVALID_ARG, "x/sums pointer is NULL");
+    if (int rc = check_aligned(nm, x_dev, row_align(nm->dim, 4), "x")) return rc;
+    if (int rc = check_aligned(nm, sums_dev, 8, "sums")) return rc;
     const int64_t leaves = ceil_div(nm->n, kObsLeafRows);
     if (int rc = ensure_capacity(nm, K, leaves, 2 * nm->dim)) return rc;
     if (int rc = dispatch_obs_sums(nm, K, x_dev, leaves)) return rc;
@@ -651,27 +630,27 @@ int mxv_norm_obs_sums(mxv_norm *nm, int32_t K, const float *x_dev, double *sums_
 
 int mxv_norm_obs_sums_partials(mxv_norm *nm, int32_t K, const double *partials_dev, int64_t leaves, double *sums_dev) {
     if (int rc = checks(nm, K)) return rc;
-    if (!partials_dev || !sums_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "partials/sums pointer is NULL");
-    if (leaves < 1) return nfail(nm, MXV_ERR_INVALID_ARG, "leaves must be positive");
-    if (int rc = norm_aligned(nm, partials_dev, 8, "partials")) return rc;
-    if (int rc = norm_aligned(nm, sums_dev, 8, "sums")) return rc;
+    if (!partials_dev || !sums_dev) return fail(nm, MXV_ERR_INVALID_ARG, "partials/sums pointer is NULL");
+    if (leaves < 1) return fail(nm, MXV_ERR_INVALID_ARG, "leaves must be positive");
+    if (int rc = check_aligned(nm, partials_dev, 8, "partials")) return rc;
+    if (int rc = check_aligned(nm, sums_dev, 8, "sums")) return rc;
     if (int rc = ensure_capacity(nm, K, ceil_div(leaves, kTreeFan), 2 * nm->dim)) return rc;
     return run_tree(nm, K, leaves, 2 * nm->dim, sums_dev, partials_dev);
 }
 
 int mxv_norm_reward_sums_partials(mxv_norm *nm, int32_t K, const double *partials_dev, int64_t leaves, double *sums_dev) {
     if (int rc = checks(nm, K)) return rc;
-    if (nm->dim != 1) return nfail(nm, MXV_ERR_INVALID_ARG, "reward sums need a 1-column mxv_norm");
-    if (!partials_dev || !sums_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "partials/sums pointer is NULL");
-    if (leaves < 1) return nfail(nm, MXV_ERR_INVALID_ARG, "leaves must be positive");
-    if (int rc = norm_aligned(nm, partials_dev, 8, "partials")) return rc;
-    if (int rc = norm_aligned(nm, sums_dev, 8, "sums")) return rc;
+    if (nm->dim != 1) return fail(nm, MXV_ERR_INVALID_ARG, "reward sums need a 1-column mxv_norm");
+    if (!partials_dev || !sums_dev) return fail(nm, MXV_ERR_INVALID_ARG, "partials/sums pointer is NULL");
+    if (leaves < 1) return fail(nm, MXV_ERR_INVALID_ARG, "leaves must be positive");
+    if (int rc = check_aligned(nm, partials_dev, 8, "partials")) return rc;
+    if (int rc = check_aligned(nm, sums_dev, 8, "sums")) return rc;
     if (int rc = ensure_capacity(nm, K, ceil_div(leaves, kTreeFan), 2)) return rc;
     return run_tree(nm, K, leaves, 2, sums_dev, partials_dev);
 }
 
 int mxv_norm_returns_ptr(mxv_norm *nm, double **returns_dev) {
-    if (!nm || !returns_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "NULL mxv_norm or output pointer");
+    if (!nm || !returns_dev) return fail(nm, MXV_ERR_INVALID_ARG, "NULL mxv_norm or output pointer");
     *returns_dev = nm->returns;
     return MXV_OK;
 }
@@ -679,10 +658,10 @@ int mxv_norm_returns_ptr(mxv_norm *nm, double **returns_dev) {
 int mxv_norm_obs_apply(mxv_norm *nm, int32_t K, const float *x_dev, void *y_dev, int32_t out_f32, double epsilon,
                        const double *all_sums_dev, int32_t world, int64_t total_rows) {
     if (int rc = checks(nm, K)) return rc;
-    if (!x_dev || !y_dev || !all_sums_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "x/y/sums pointer is NULL");
-    if (int rc = norm_aligned(nm, x_dev, row_align(nm->dim, 4), "x")) return rc;
-    if (int rc = norm_aligned(nm, y_dev, row_align(nm->dim, out_f32 ? 4 : 8), "y")) return rc;
-    if (int rc = norm_aligned(nm, all_sums_dev, 8, "sums")) return rc;
+    if (!x_dev || !y_dev || !all_sums_dev) return fail(nm, MXV_ERR_INVALID_ARG, "x/y/sums pointer is NULL");
+    if (int rc = check_aligned(nm, x_dev, row_align(nm->dim, 4), "x")) return rc;
+    if (int rc = check_aligned(nm, y_dev, row_align(nm->dim, out_f32 ? 4 : 8), "y")) return rc;
+    if (int rc = check_aligned(nm, all_sums_dev, 8, "sums")) return rc;
     if (int rc = ensure_capacity(nm, K, 1, 2 * nm->dim)) return rc;
     if (int rc = run_scan(nm, K, all_sums_dev, world, total_rows, epsilon, 1)) return rc;
     return dispatch_obs_apply(nm, K, x_dev, y_dev, out_f32);
@@ -690,9 +669,9 @@ int mxv_norm_obs_apply(mxv_norm *nm, int32_t K, const float *x_dev, void *y_dev,
 
 int mxv_norm_observations(mxv_norm *nm, int32_t K, const float *x_dev, void *y_dev, int32_t out_f32, double epsilon) {
     if (int rc = checks(nm, K)) return rc;
-    if (!x_dev || !y_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "x/y pointer is NULL");
-    if (int rc = norm_aligned(nm, x_dev, row_align(nm->dim, 4), "x")) return rc;
-    if (int rc = norm_aligned(nm, y_dev, row_align(nm->dim, out_f32 ? 4 : 8), "y")) return rc;
+    if (!x_dev || !y_dev) return fail(nm, MXV_ERR_INVALID_ARG, "x/y pointer is NULL");
+    if (int rc = check_aligned(nm, x_dev, row_align(nm->dim, 4), "x")) return rc;
+    if (int rc = check_aligned(nm, y_dev, row_align(nm->dim, out_f32 ? 4 : 8), "y")) return rc;
     const int64_t leaves = ceil_div(nm->n, kObsLeafRows);
     if (int rc = ensure_capacity(nm, K, leaves, 2 * nm->dim)) return rc;
     if (int rc = mxv_norm_obs_sums(nm, K, x_dev, nm->sums)) return rc;
@@ -702,11 +681,11 @@ int mxv_norm_observations(mxv_norm *nm, int32_t K, const float *x_dev, void *y_d
 int mxv_norm_reward_sums(mxv_norm *nm, int32_t K, const void *reward_dev, int32_t reward_f32, const uint8_t *terminated_dev,
                          const uint8_t *truncated_dev, double gamma, double *sums_dev) {
     if (int rc = checks(nm, K)) return rc;
-    if (nm->dim != 1) return nfail(nm, MXV_ERR_INVALID_ARG, "reward statistics need dim == 1 (RunningMeanStd(shape=()))");
+    if (nm->dim != 1) return fail(nm, MXV_ERR_INVALID_ARG, "reward statistics need dim == 1 (RunningMeanStd(shape=()))");
     if (!reward_dev || !terminated_dev || !truncated_dev || !sums_dev)
-        return nfail(nm, MXV_ERR_INVALID_ARG, "reward/terminated/truncated/sums pointer is NULL");
-    if (int rc = norm_aligned(nm, reward_dev, reward_f32 ? 4 : 8, "reward")) return rc;
-    if (int rc = norm_aligned(nm, sums_dev, 8, "sums")) return rc;
+        return fail(nm, MXV_ERR_INVALID_ARG, "reward/terminated/truncated/sums pointer is NULL");
+    if (int rc = check_aligned(nm, reward_dev, reward_f32 ? 4 : 8, "reward")) return rc;
+    if (int rc = check_aligned(nm, sums_dev, 8, "sums")) return rc;
     const int64_t leaves = ceil_div(nm->n, kRewLeafEnvs);
     if (int rc = ensure_capacity(nm, K, leaves, 2)) return rc;
     // the vector loads (16 / 32 bytes of rewards, 4 of each flag array per lane) need tensors that start on those boundaries — true of
@@ -718,18 +697,18 @@ int mxv_norm_reward_sums(mxv_norm *nm, int32_t K, const void *reward_dev, int32_
     else
         hipLaunchKernelGGL(returns_sums_kernel<double>, dim3((unsigned)leaves), dim3(64), 0, nm->stream, (const double *)reward_dev,
                            terminated_dev, truncated_dev, nm->returns, nm->n, (int)K, gamma, leaves, nm->part_a, aligned);
-    NRM_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return run_tree(nm, K, leaves, 2, sums_dev);
 }
 
 int mxv_norm_reward_apply(mxv_norm *nm, int32_t K, const void *reward_dev, int32_t reward_f32, void *out_dev, double epsilon,
                           const double *all_sums_dev, int32_t world, int64_t total_rows) {
     if (int rc = checks(nm, K)) return rc;
-    if (nm->dim != 1) return nfail(nm, MXV_ERR_INVALID_ARG, "reward statistics need dim == 1 (RunningMeanStd(shape=()))");
-    if (!reward_dev || !out_dev || !all_sums_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "reward/out/sums pointer is NULL");
-    if (int rc = norm_aligned(nm, reward_dev, reward_f32 ? 4 : 8, "reward")) return rc;
-    if (int rc = norm_aligned(nm, out_dev, reward_f32 ? 4 : 8, "out")) return rc;
-    if (int rc = norm_aligned(nm, all_sums_dev, 8, "sums")) return rc;
+    if (nm->dim != 1) return fail(nm, MXV_ERR_INVALID_ARG, "reward statistics need dim == 1 (RunningMeanStd(shape=()))");
+    if (!reward_dev || !out_dev || !all_sums_dev) return fail(nm, MXV_ERR_INVALID_ARG, "reward/out/sums pointer is NULL");
+    if (int rc = check_aligned(nm, reward_dev, reward_f32 ? 4 : 8, "reward")) return rc;
+    if (int rc = check_aligned(nm, out_dev, reward_f32 ? 4 : 8, "out")) return rc;
+    if (int rc = check_aligned(nm, all_sums_dev, 8, "sums")) return rc;
     if (int rc = ensure_capacity(nm, K, 1, 2)) return rc;
     if (int rc = run_scan(nm, K, all_sums_dev, world, total_rows, epsilon, 0)) return rc;
     const int V = reward_f32 ? 4 : 2;
@@ -750,15 +729,15 @@ int mxv_norm_reward_apply(mxv_norm *nm, int32_t K, const void *reward_dev, int32
             hipLaunchKernelGGL((reward_apply_kernel<double, 1>), grid, dim3(kThreads), 0, nm->stream, (const double *)reward_dev,
                                (double *)out_dev, nm->coef, nm->n);
     }
-    NRM_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return MXV_OK;
 }
 
 int mxv_norm_rewards(mxv_norm *nm, int32_t K, const void *reward_dev, int32_t reward_f32, const uint8_t *terminated_dev,
                      const uint8_t *truncated_dev, void *out_dev, double gamma, double epsilon) {
     if (int rc = checks(nm, K)) return rc;
-    if (!out_dev) return nfail(nm, MXV_ERR_INVALID_ARG, "out pointer is NULL");
-    if (int rc = norm_aligned(nm, out_dev, reward_f32 ? 4 : 8, "out")) return rc;
+    if (!out_dev) return fail(nm, MXV_ERR_INVALID_ARG, "out pointer is NULL");
+    if (int rc = check_aligned(nm, out_dev, reward_f32 ? 4 : 8, "out")) return rc;
     const int64_t leaves = ceil_div(nm->n, kRewLeafEnvs);
     if (int rc = ensure_capacity(nm, K, leaves, 2)) return rc;
     if (int rc = mxv_norm_reward_sums(nm, K, reward_dev, reward_f32, terminated_dev, truncated_dev, gamma, nm->sums)) return rc;

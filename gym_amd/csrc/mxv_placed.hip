@@ -28,8 +28,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <initializer_list>
 #include <new>
@@ -38,10 +36,13 @@
 
 #include "../../include/mxv.h"
 #include "../../include/mxv_diag.h"
+#include "mxv_host.hpp"
+
+using mxv::fail;
+using mxv::last_error;
 
 namespace {
 
-thread_local std::string g_placed_error;
 constexpr size_t kChunk = MXV_PLACED_CHUNK_BYTES;
 constexpr int64_t kProbeLanes = 1 << 20;   // the classification probe is the 2^20-env CartPole window: 16 steps x 16 B = one chunk
 constexpr int kProbeSteps = 16;
@@ -79,8 +80,6 @@ struct Tensor {
     void *plain = nullptr;     // hipMalloc path
 };
 
-int pfail(mxv_placed *p, int code, const char *fmt, ...);
-
 }  // namespace
 
 struct mxv_placed {
@@ -93,24 +92,6 @@ struct mxv_placed {
 };
 
 namespace {
-
-int pfail(mxv_placed *p, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (p)
-        p->error = buf;
-    g_placed_error = buf;
-    return code;
-}
-
-#define PL_HIP(p, expr)                                                                                 \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return pfail((p), MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
 
 struct Prober {
     hipStream_t stream = nullptr;
@@ -157,7 +138,7 @@ struct Prober {
 
 int new_chunk(mxv_placed *p, Prober &pr) {
     Chunk c;
-    PL_HIP(p, hipMemCreate(&c.handle, kChunk, &pr.prop, 0));
+    MXV_HIP(p, hipMemCreate(&c.handle, kChunk, &pr.prop, 0));
     hipError_t e = hipMemAddressReserve(reinterpret_cast<void **>(&c.scratch), kChunk, 0, nullptr, 0);
     if (e == hipSuccess) e = hipMemMap(c.scratch, kChunk, 0, c.handle, 0);
     if (e == hipSuccess) {
@@ -166,7 +147,7 @@ int new_chunk(mxv_placed *p, Prober &pr) {
     }
     p->chunks.push_back(c);
     p->info.chunks_created++;
-    if (e != hipSuccess) return pfail(p, MXV_ERR_HIP, "mapping a %zu-MiB chunk for classification: %s", kChunk >> 20, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(p, MXV_ERR_HIP, "mapping a %zu-MiB chunk for classification: %s", kChunk >> 20, hipGetErrorString(e));
     return MXV_OK;
 }
 
@@ -183,7 +164,7 @@ void drop_chunk(Chunk &c) {
 
 extern "C" {
 
-const char *mxv_placed_last_error(const mxv_placed *p) { return p ? p->error.c_str() : g_placed_error.c_str(); }
+const char *mxv_placed_last_error(const mxv_placed *p) { return last_error(p); }
 
 int mxv_placed_free(mxv_placed *p) {
     if (!p) return MXV_OK;
@@ -201,8 +182,8 @@ int mxv_placed_free(mxv_placed *p) {
 }
 
 int mxv_hbm_pair_probe(int32_t device, void *wide_dev, void *narrow_dev, int32_t launches, double *us_per_step) {
-    if (!wide_dev || !narrow_dev || !us_per_step || launches < 1) return pfail(nullptr, MXV_ERR_INVALID_ARG, "mxv_hbm_pair_probe: NULL argument");
-    if (hipSetDevice(device) != hipSuccess) return pfail(nullptr, MXV_ERR_HIP, "hipSetDevice(%d) failed", device);
+    if (!wide_dev || !narrow_dev || !us_per_step || launches < 1) return fail<mxv_placed>(nullptr, MXV_ERR_INVALID_ARG, "mxv_hbm_pair_probe: NULL argument");
+    if (hipSetDevice(device) != hipSuccess) return fail<mxv_placed>(nullptr, MXV_ERR_HIP, "hipSetDevice(%d) failed", device);
     // the window writes 256 MiB behind wide_dev and 128 MiB behind narrow_dev: the sizes are part of the contract, so they are checked
     // against the allocations the pointers belong to (a short buffer would be a device fault, i.e. the caller's process)
     const struct { void *p; size_t need; const char *what; } spans[] = {{wide_dev, (size_t)256 << 20, "wide_dev"}, {narrow_dev, (size_t)128 << 20, "narrow_dev"}};
@@ -211,39 +192,39 @@ int mxv_hbm_pair_probe(int32_t device, void *wide_dev, void *narrow_dev, int32_t
         size_t size = 0;
         if (hipMemGetAddressRange(&base, &size, sp.p) != hipSuccess || !base) {
             (void)hipGetLastError();
-            return pfail(nullptr, MXV_ERR_INVALID_ARG, "mxv_hbm_pair_probe: %s is not inside a device allocation", sp.what);
+            return fail<mxv_placed>(nullptr, MXV_ERR_INVALID_ARG, "mxv_hbm_pair_probe: %s is not inside a device allocation", sp.what);
         }
         const size_t off = (size_t)((char *)sp.p - (char *)base);
         if (((uintptr_t)sp.p & 15) != 0 || off > size || size - off < sp.need)
-            return pfail(nullptr, MXV_ERR_INVALID_ARG, "mxv_hbm_pair_probe: %s needs %zu MiB of 16-byte aligned device memory behind it (%zu bytes there)",
+            return fail<mxv_placed>(nullptr, MXV_ERR_INVALID_ARG, "mxv_hbm_pair_probe: %s needs %zu MiB of 16-byte aligned device memory behind it (%zu bytes there)",
                          sp.what, sp.need >> 20, off <= size ? size - off : (size_t)0);
     }
     Prober pr;
-    if (hipError_t e = pr.init(device); e != hipSuccess) return pfail(nullptr, MXV_ERR_HIP, "stream / events: %s", hipGetErrorString(e));
+    if (hipError_t e = pr.init(device); e != hipSuccess) return fail<mxv_placed>(nullptr, MXV_ERR_HIP, "stream / events: %s", hipGetErrorString(e));
     Chunk w, n;
     w.scratch = static_cast<char *>(wide_dev);
     n.scratch = static_cast<char *>(narrow_dev);
     float us = 0.f;
     hipError_t e = pr.time_pair(w, n, 2, 1, &us);   // first touch
     if (e == hipSuccess) e = pr.time_pair(w, n, launches, 3, &us);
-    if (e != hipSuccess) return pfail(nullptr, MXV_ERR_HIP, "mxv_hbm_pair_probe: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail<mxv_placed>(nullptr, MXV_ERR_HIP, "mxv_hbm_pair_probe: %s", hipGetErrorString(e));
     *us_per_step = us;
     return MXV_OK;
 }
 
 int mxv_placed_info_get(const mxv_placed *p, mxv_placed_info *out) {
-    if (!p || !out) return pfail(nullptr, MXV_ERR_INVALID_ARG, "mxv_placed_info_get: NULL argument");
+    if (!p || !out) return fail<mxv_placed>(nullptr, MXV_ERR_INVALID_ARG, "mxv_placed_info_get: NULL argument");
     *out = p->info;
     return MXV_OK;
 }
 
 int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const int32_t *group, int32_t flags, void **ptrs_out, mxv_placed **out) {
-    if (count < 1 || !bytes || !group || !ptrs_out || !out) return pfail(nullptr, MXV_ERR_INVALID_ARG, "mxv_placed_alloc: NULL argument or count < 1");
+    if (count < 1 || !bytes || !group || !ptrs_out || !out) return fail<mxv_placed>(nullptr, MXV_ERR_INVALID_ARG, "mxv_placed_alloc: NULL argument or count < 1");
     for (int i = 0; i < count; ++i)
-        if (bytes[i] == 0 || group[i] < -1 || group[i] > 1) return pfail(nullptr, MXV_ERR_INVALID_ARG, "mxv_placed_alloc: tensor %d: bytes > 0 and group in {-1, 0, 1}", i);
+        if (bytes[i] == 0 || group[i] < -1 || group[i] > 1) return fail<mxv_placed>(nullptr, MXV_ERR_INVALID_ARG, "mxv_placed_alloc: tensor %d: bytes > 0 and group in {-1, 0, 1}", i);
     const auto t_begin = std::chrono::steady_clock::now();
     mxv_placed *p = new (std::nothrow) mxv_placed;
-    if (!p) return pfail(nullptr, MXV_ERR_HIP, "out of host memory");
+    if (!p) return fail<mxv_placed>(nullptr, MXV_ERR_HIP, "out of host memory");
     p->device = device;
     p->tensors.resize(count);
     size_t total = 0;
@@ -259,16 +240,16 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
     auto bail = [&](int rc) {
         std::string msg = p->error;
         mxv_placed_free(p);
-        g_placed_error = msg;
+        mxv::create_error<mxv_placed>() = msg;
         return rc;
     };
-    if (hipSetDevice(device) != hipSuccess) return bail(pfail(p, MXV_ERR_HIP, "hipSetDevice(%d) failed", device));
+    if (hipSetDevice(device) != hipSuccess) return bail(fail(p, MXV_ERR_HIP, "hipSetDevice(%d) failed", device));
     p->info.requested_bytes = total;
     const bool want_placed = !(flags & MXV_PLACED_PLAIN) && need[0] > 0 && need[1] > 0 && total >= MXV_PLACED_MIN_BYTES;
     if (!want_placed) {   // small sets (the modes were only ever seen from about a GiB) and one-group sets: ordinary allocations
         for (int i = 0; i < count; ++i) {
             hipError_t e = hipMalloc(&p->tensors[i].plain, bytes[i]);
-            if (e != hipSuccess) return bail(pfail(p, MXV_ERR_HIP, "hipMalloc(%zu): %s", bytes[i], hipGetErrorString(e)));
+            if (e != hipSuccess) return bail(fail(p, MXV_ERR_HIP, "hipMalloc(%zu): %s", bytes[i], hipGetErrorString(e)));
             ptrs_out[i] = p->tensors[i].plain;
         }
         p->info.held_bytes = total;
@@ -277,7 +258,7 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
     }
 
     Prober pr;
-    if (hipError_t e = pr.init(device); e != hipSuccess) return bail(pfail(p, MXV_ERR_HIP, "stream / events: %s", hipGetErrorString(e)));
+    if (hipError_t e = pr.init(device); e != hipSuccess) return bail(fail(p, MXV_ERR_HIP, "stream / events: %s", hipGetErrorString(e)));
     const int needed = need[0] + need[1] + need[2];
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
@@ -291,7 +272,7 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
 #define PL_TIME(w, n, launches, reps, out)                                                                                      \
     do {                                                                                                                        \
         if (hipError_t e_ = pr.time_pair(p->chunks[w], p->chunks[n], launches, reps, out); e_ != hipSuccess)                     \
-            return bail(pfail(p, MXV_ERR_HIP, "classification probe: %s", hipGetErrorString(e_)));                               \
+            return bail(fail(p, MXV_ERR_HIP, "classification probe: %s", hipGetErrorString(e_)));                               \
     } while (0)
     // Bootstrap on the first three chunks, timed pairwise.  Created back to back they come from one neighbourhood: if all three
     // pairings agree they share a class and (0, 1) is the calibration pair; if one pairing is clearly slower than the fastest, that
@@ -400,7 +381,7 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
             for (size_t b = 0; b < kSpacer && !failed; b += kChunk) {
                 hipMemGenericAllocationHandle_t h;
                 if (hipError_t e = hipMemCreate(&h, kChunk, &pr.prop, 0); e != hipSuccess) {
-                    pfail(p, MXV_ERR_HIP, "spacer hipMemCreate(%zu): %s", kChunk, hipGetErrorString(e));
+                    fail(p, MXV_ERR_HIP, "spacer hipMemCreate(%zu): %s", kChunk, hipGetErrorString(e));
                     failed = true;
                 } else {
                     spacers.push_back(h);
@@ -440,7 +421,7 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
         solo_class = 0;
         for (int k = 1; k < kMaxClasses; ++k) if (have[k] > have[solo_class]) solo_class = k;
     }
-    if (live() < needed) return bail(pfail(p, MXV_ERR_HIP, "mxv_placed_alloc: %d chunks of %zu MiB needed, %d available (out of device memory?)", needed, kChunk >> 20, live()));
+    if (live() < needed) return bail(fail(p, MXV_ERR_HIP, "mxv_placed_alloc: %d chunks of %zu MiB needed, %d available (out of device memory?)", needed, kChunk >> 20, live()));
 
     // hand out: the solo group from its class; the other group from the other classes (then from anything); group -1 from what nobody wants
     std::vector<int> pool_solo, pool_other, pool_any;
@@ -464,7 +445,7 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
                 if (pass == 0) { c = take({&pool_solo, &pool_any, &pool_other}); if (c >= 0 && p->chunks[c].klass != solo_class) mismatched++; }
                 else if (pass == 1) { c = take({&pool_other, &pool_any, &pool_solo}); if (c >= 0 && (p->chunks[c].klass < 0 || p->chunks[c].klass == solo_class)) mismatched++; }
                 else c = take({&pool_any, pool_solo.size() >= pool_other.size() ? &pool_solo : &pool_other, pool_solo.size() >= pool_other.size() ? &pool_other : &pool_solo});
-                if (c < 0) return bail(pfail(p, MXV_ERR_HIP, "mxv_placed_alloc: ran out of chunks"));
+                if (c < 0) return bail(fail(p, MXV_ERR_HIP, "mxv_placed_alloc: ran out of chunks"));
                 t.chunks.push_back(c);
             }
         }
@@ -474,7 +455,7 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
     for (int i = 0; i < count; ++i) {
         Tensor &t = p->tensors[i];
         hipError_t e = hipMemAddressReserve(reinterpret_cast<void **>(&t.va), t.reserved, 0, nullptr, 0);
-        if (e != hipSuccess) return bail(pfail(p, MXV_ERR_HIP, "hipMemAddressReserve(%zu): %s", t.reserved, hipGetErrorString(e)));
+        if (e != hipSuccess) return bail(fail(p, MXV_ERR_HIP, "hipMemAddressReserve(%zu): %s", t.reserved, hipGetErrorString(e)));
         for (size_t j = 0; j < t.chunks.size(); ++j) {
             Chunk &c = p->chunks[t.chunks[j]];
             if (c.scratch_mapped) {
@@ -483,13 +464,13 @@ int mxv_placed_alloc(int32_t device, int32_t count, const size_t *bytes, const i
             }
             if ((e = hipMemMap(t.va + j * kChunk, kChunk, 0, c.handle, 0)) != hipSuccess) {
                 t.chunks.resize(j);
-                return bail(pfail(p, MXV_ERR_HIP, "hipMemMap: %s", hipGetErrorString(e)));
+                return bail(fail(p, MXV_ERR_HIP, "hipMemMap: %s", hipGetErrorString(e)));
             }
         }
-        if ((e = hipMemSetAccess(t.va, t.reserved, &pr.acc, 1)) != hipSuccess) return bail(pfail(p, MXV_ERR_HIP, "hipMemSetAccess: %s", hipGetErrorString(e)));
+        if ((e = hipMemSetAccess(t.va, t.reserved, &pr.acc, 1)) != hipSuccess) return bail(fail(p, MXV_ERR_HIP, "hipMemSetAccess: %s", hipGetErrorString(e)));
         ptrs_out[i] = t.va;
     }
-    if (hipError_t e = hipStreamSynchronize(pr.stream); e != hipSuccess) return bail(pfail(p, MXV_ERR_HIP, "%s", hipGetErrorString(e)));
+    if (hipError_t e = hipStreamSynchronize(pr.stream); e != hipSuccess) return bail(fail(p, MXV_ERR_HIP, "%s", hipGetErrorString(e)));
     p->info.placed = 1;
     p->info.balanced = balanced && mismatched == 0;
     p->info.chunks_kept = needed;

@@ -22,15 +22,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/mxv.h"
 #include "mxv_divide.hpp"
+#include "mxv_host.hpp"
+
+using mxv::check_aligned;
+using mxv::fail;
+using mxv::last_error;
 
 namespace {
 
@@ -254,6 +257,7 @@ __global__ void __launch_bounds__(kThreads) subnorm_rew_kernel(const SubRewArgs 
 }  // namespace
 
 struct mxv_subnorm {
+    static constexpr const char *kNullMessage = "NULL mxv_subnorm";
     int device = 0, dim = 0;
     int64_t n = 0;
     hipStream_t stream = nullptr;
@@ -264,34 +268,13 @@ struct mxv_subnorm {
 
 namespace {
 
-thread_local std::string g_subnorm_create_error;
-
-int sfail(mxv_subnorm *nm, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (nm)
-        nm->error = buf;
-    else
-        g_subnorm_create_error = buf;
-    return code;
-}
-
-#define SUB_HIP(nm, expr)                                                                               \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return sfail((nm), MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 bool sub_dim_supported(int d) { return d == 1 || d == 2 || d == 3 || d == 4 || d == 6; }
 
 int sub_checks(mxv_subnorm *nm, int32_t K) {
-    if (!nm) return sfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_subnorm");
-    if (K <= 0) return sfail(nm, MXV_ERR_INVALID_ARG, "K must be positive (got %d)", K);
-    if ((int64_t)K * nm->n > ((int64_t)1 << 40)) return sfail(nm, MXV_ERR_INVALID_ARG, "K * num_envs too large");
-    SUB_HIP(nm, hipSetDevice(nm->device));
+    MXV_CHECK(nm);
+    if (K <= 0) return fail(nm, MXV_ERR_INVALID_ARG, "K must be positive (got %d)", K);
+    if ((int64_t)K * nm->n > ((int64_t)1 << 40)) return fail(nm, MXV_ERR_INVALID_ARG, "K * num_envs too large");
+    MXV_HIP(nm, hipSetDevice(nm->device));
     return MXV_OK;
 }
 
@@ -300,8 +283,8 @@ int init_stats(mxv_subnorm *nm) {  // RunningMeanStd.__init__: mean 0, var 1, co
     std::vector<double> init((size_t)(2 * nm->dim + 1) * n, 0.0);
     for (size_t i = (size_t)nm->dim * n; i < (size_t)(2 * nm->dim) * n; ++i) init[i] = 1.0;
     for (size_t i = (size_t)(2 * nm->dim) * n; i < init.size(); ++i) init[i] = 1e-4;
-    SUB_HIP(nm, hipMemcpy(nm->stat, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
-    SUB_HIP(nm, hipMemset(nm->returns, 0, n * sizeof(double)));  // np.zeros(num_envs), :123
+    MXV_HIP(nm, hipMemcpy(nm->stat, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+    MXV_HIP(nm, hipMemset(nm->returns, 0, n * sizeof(double)));  // np.zeros(num_envs), :123
     return MXV_OK;
 }
 
@@ -315,7 +298,7 @@ int launch_obs(mxv_subnorm *nm, const SubObsArgs &a) {
         case 4: hipLaunchKernelGGL((subnorm_obs_kernel<4, OUT>), grid, block, 0, nm->stream, a); break;
         default: hipLaunchKernelGGL((subnorm_obs_kernel<6, OUT>), grid, block, 0, nm->stream, a); break;
     }
-    SUB_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return MXV_OK;
 }
 
@@ -324,18 +307,18 @@ int launch_obs(mxv_subnorm *nm, const SubObsArgs &a) {
 extern "C" {
 
 int mxv_subnorm_create(int32_t device, int32_t dim, int64_t num_envs, void *stream, mxv_subnorm **out) {
-    if (!out) return sfail(nullptr, MXV_ERR_INVALID_ARG, "NULL output pointer");
+    if (!out) return fail<mxv_subnorm>(nullptr, MXV_ERR_INVALID_ARG, "NULL output pointer");
     *out = nullptr;
-    if (!sub_dim_supported(dim)) return sfail(nullptr, MXV_ERR_UNSUPPORTED, "dim must be one of 1, 2, 3, 4, 6 (got %d)", dim);
-    if (num_envs <= 0 || num_envs > ((int64_t)1 << 31)) return sfail(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be in 1 .. 2^31");
+    if (!sub_dim_supported(dim)) return fail<mxv_subnorm>(nullptr, MXV_ERR_UNSUPPORTED, "dim must be one of 1, 2, 3, 4, 6 (got %d)", dim);
+    if (num_envs <= 0 || num_envs > ((int64_t)1 << 31)) return fail<mxv_subnorm>(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be in 1 .. 2^31");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
-        return sfail(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
+        return fail<mxv_subnorm>(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
                      e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (device < 0 || device >= ndev) return sfail(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", device);
+    if (device < 0 || device >= ndev) return fail<mxv_subnorm>(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", device);
     mxv_subnorm *nm = new (std::nothrow) mxv_subnorm();
-    if (!nm) return sfail(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
+    if (!nm) return fail<mxv_subnorm>(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
     nm->device = device;
     nm->dim = dim;
     nm->n = num_envs;
@@ -344,7 +327,7 @@ int mxv_subnorm_create(int32_t device, int32_t dim, int64_t num_envs, void *stre
     if (err == hipSuccess) err = hipMalloc((void **)&nm->stat, (size_t)(2 * dim + 1) * (size_t)num_envs * sizeof(double));
     if (err == hipSuccess) err = hipMalloc((void **)&nm->returns, (size_t)num_envs * sizeof(double));
     if (err != hipSuccess || init_stats(nm) != MXV_OK) {
-        sfail(nullptr, MXV_ERR_HIP, "mxv_subnorm_create: %s", err != hipSuccess ? hipGetErrorString(err) : nm->error.c_str());
+        fail<mxv_subnorm>(nullptr, MXV_ERR_HIP, "mxv_subnorm_create: %s", err != hipSuccess ? hipGetErrorString(err) : nm->error.c_str());
         mxv_subnorm_destroy(nm);
         return MXV_ERR_HIP;
     }
@@ -362,24 +345,24 @@ int mxv_subnorm_destroy(mxv_subnorm *nm) {
     return MXV_OK;
 }
 
-const char *mxv_subnorm_last_error(const mxv_subnorm *nm) { return nm ? nm->error.c_str() : g_subnorm_create_error.c_str(); }
+const char *mxv_subnorm_last_error(const mxv_subnorm *nm) { return last_error(nm); }
 
 int mxv_subnorm_set_stream(mxv_subnorm *nm, void *stream) {
-    if (!nm) return sfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_subnorm");
-    SUB_HIP(nm, hipSetDevice(nm->device));
-    SUB_HIP(nm, hipStreamSynchronize(nm->stream));
+    MXV_CHECK(nm);
+    MXV_HIP(nm, hipSetDevice(nm->device));
+    MXV_HIP(nm, hipStreamSynchronize(nm->stream));
     nm->stream = (hipStream_t)stream;
     return MXV_OK;
 }
 
 int mxv_subnorm_get_state(mxv_subnorm *nm, double *mean_host, double *var_host, double *count_host, double *returns_host) {
-    if (!nm) return sfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_subnorm");
-    SUB_HIP(nm, hipSetDevice(nm->device));
+    MXV_CHECK(nm);
+    MXV_HIP(nm, hipSetDevice(nm->device));
     const size_t n = (size_t)nm->n, D = (size_t)nm->dim;
     std::vector<double> st((2 * D + 1) * n);
-    SUB_HIP(nm, hipMemcpyAsync(st.data(), nm->stat, st.size() * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
-    if (returns_host) SUB_HIP(nm, hipMemcpyAsync(returns_host, nm->returns, n * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
-    SUB_HIP(nm, hipStreamSynchronize(nm->stream));
+    MXV_HIP(nm, hipMemcpyAsync(st.data(), nm->stat, st.size() * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
+    if (returns_host) MXV_HIP(nm, hipMemcpyAsync(returns_host, nm->returns, n * sizeof(double), hipMemcpyDeviceToHost, nm->stream));
+    MXV_HIP(nm, hipStreamSynchronize(nm->stream));
     for (size_t i = 0; i < n; ++i) {  // device layout [2 D + 1][n] -> the wrappers' per-env arrays [n][D]
         for (size_t j = 0; j < D; ++j) {
             if (mean_host) mean_host[i * D + j] = st[j * n + i];
@@ -392,9 +375,9 @@ int mxv_subnorm_get_state(mxv_subnorm *nm, double *mean_host, double *var_host, 
 
 int mxv_subnorm_set_state(mxv_subnorm *nm, const double *mean_host, const double *var_host, const double *count_host,
                           const double *returns_host) {
-    if (!nm) return sfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_subnorm");
-    if (!mean_host || !var_host || !count_host) return sfail(nm, MXV_ERR_INVALID_ARG, "mean / var / count pointer is NULL");
-    SUB_HIP(nm, hipSetDevice(nm->device));
+    MXV_CHECK(nm);
+    if (!mean_host || !var_host || !count_host) return fail(nm, MXV_ERR_INVALID_ARG, "mean / var / count pointer is NULL");
+    MXV_HIP(nm, hipSetDevice(nm->device));
     const size_t n = (size_t)nm->n, D = (size_t)nm->dim;
     std::vector<double> st((2 * D + 1) * n);
     for (size_t i = 0; i < n; ++i) {
@@ -404,29 +387,29 @@ int mxv_subnorm_set_state(mxv_subnorm *nm, const double *mean_host, const double
         }
         st[2 * D * n + i] = count_host[i];
     }
-    SUB_HIP(nm, hipMemcpyAsync(nm->stat, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, nm->stream));
-    if (returns_host) SUB_HIP(nm, hipMemcpyAsync(nm->returns, returns_host, n * sizeof(double), hipMemcpyHostToDevice, nm->stream));
-    SUB_HIP(nm, hipStreamSynchronize(nm->stream));
+    MXV_HIP(nm, hipMemcpyAsync(nm->stat, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, nm->stream));
+    if (returns_host) MXV_HIP(nm, hipMemcpyAsync(nm->returns, returns_host, n * sizeof(double), hipMemcpyHostToDevice, nm->stream));
+    MXV_HIP(nm, hipStreamSynchronize(nm->stream));
     return MXV_OK;
 }
 
 int mxv_subnorm_observations(mxv_subnorm *nm, int32_t K, const float *x_dev, const float *final_dev, const uint8_t *terminated_dev,
                              const uint8_t *truncated_dev, void *y_dev, int32_t out_f32, double *final_y_dev, double epsilon) {
     if (int rc = sub_checks(nm, K)) return rc;
-    if (!x_dev || !y_dev) return sfail(nm, MXV_ERR_INVALID_ARG, "x / y pointer is NULL");
+    if (!x_dev || !y_dev) return fail(nm, MXV_ERR_INVALID_ARG, "x / y pointer is NULL");
     if ((terminated_dev == nullptr) != (truncated_dev == nullptr))
-        return sfail(nm, MXV_ERR_INVALID_ARG, "terminated and truncated go together (both NULL: nobody has finished, the reset() form)");
-    if (final_dev && !terminated_dev) return sfail(nm, MXV_ERR_INVALID_ARG, "terminal observations without the flags that say whose they are");
-    if (final_y_dev && !final_dev) return sfail(nm, MXV_ERR_INVALID_ARG, "final_y without the terminal observations");
+        return fail(nm, MXV_ERR_INVALID_ARG, "terminated and truncated go together (both NULL: nobody has finished, the reset() form)");
+    if (final_dev && !terminated_dev) return fail(nm, MXV_ERR_INVALID_ARG, "terminal observations without the flags that say whose they are");
+    if (final_y_dev && !final_dev) return fail(nm, MXV_ERR_INVALID_ARG, "final_y without the terminal observations");
     if (!out_f32 && (const void *)x_dev == (const void *)y_dev)
-        return sfail(nm, MXV_ERR_INVALID_ARG, "float64 results cannot alias the float32 observations");
+        return fail(nm, MXV_ERR_INVALID_ARG, "float64 results cannot alias the float32 observations");
     {   // rows on the boundary of the vector width the kernel moves them with
         const int D = nm->dim;
         const size_t a32 = D % 4 == 0 ? 16 : (D % 2 == 0 ? 8 : 4), a64 = D % 2 == 0 ? 16 : 8;
         const struct { const void *p; size_t b; const char *what; } t[] = {{x_dev, a32, "x"}, {final_dev, a32, "final"}, {y_dev, out_f32 ? a32 : a64, "y"},
                                                                            {final_y_dev, a64, "final_y"}};
         for (const auto &e : t)
-            if (e.p && ((uintptr_t)e.p & (e.b - 1)) != 0) return sfail(nm, MXV_ERR_INVALID_ARG, "%s pointer %p is not %zu-byte aligned", e.what, e.p, e.b);
+            if (int rc = check_aligned(nm, e.p, e.b, e.what)) return rc;
     }
     SubObsArgs a{x_dev, final_dev, terminated_dev, truncated_dev, y_dev, final_y_dev, nm->stat, nm->n, K, epsilon};
     return out_f32 ? launch_obs<float>(nm, a) : launch_obs<double>(nm, a);
@@ -435,17 +418,17 @@ int mxv_subnorm_observations(mxv_subnorm *nm, int32_t K, const float *x_dev, con
 int mxv_subnorm_rewards(mxv_subnorm *nm, int32_t K, const void *reward_dev, int32_t reward_f32, const uint8_t *terminated_dev,
                         const uint8_t *truncated_dev, void *out_dev, double gamma, double epsilon) {
     if (int rc = sub_checks(nm, K)) return rc;
-    if (nm->dim != 1) return sfail(nm, MXV_ERR_INVALID_ARG, "reward statistics need dim == 1 (got %d)", nm->dim);
-    if (!reward_dev || !terminated_dev || !truncated_dev || !out_dev) return sfail(nm, MXV_ERR_INVALID_ARG, "NULL device pointer");
+    if (nm->dim != 1) return fail(nm, MXV_ERR_INVALID_ARG, "reward statistics need dim == 1 (got %d)", nm->dim);
+    if (!reward_dev || !terminated_dev || !truncated_dev || !out_dev) return fail(nm, MXV_ERR_INVALID_ARG, "NULL device pointer");
     if ((((uintptr_t)reward_dev | (uintptr_t)out_dev) & (reward_f32 ? 3u : 7u)) != 0)
-        return sfail(nm, MXV_ERR_INVALID_ARG, "reward / out pointer is not %d-byte aligned", reward_f32 ? 4 : 8);
+        return fail(nm, MXV_ERR_INVALID_ARG, "reward / out pointer is not %d-byte aligned", reward_f32 ? 4 : 8);
     SubRewArgs a{reward_dev, terminated_dev, truncated_dev, out_dev, nm->stat, nm->returns, nm->n, K, gamma, epsilon};
     const dim3 grid((unsigned)((a.n + kThreads - 1) / kThreads)), block(kThreads);
     if (reward_f32)
         hipLaunchKernelGGL(subnorm_rew_kernel<float>, grid, block, 0, nm->stream, a);
     else
         hipLaunchKernelGGL(subnorm_rew_kernel<double>, grid, block, 0, nm->stream, a);
-    SUB_HIP(nm, hipGetLastError());
+    MXV_HIP(nm, hipGetLastError());
     return MXV_OK;
 }
 

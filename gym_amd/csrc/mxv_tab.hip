@@ -28,14 +28,12 @@
 #include <type_traits>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "mxv_device.hpp"
+#include "mxv_host.hpp"
 
 using namespace mxv;
 
@@ -417,9 +415,6 @@ __global__ void __launch_bounds__(kTabBlock) tab_traj_kernel(TabTrajArgs a) {
     }
 }
 
-__global__ void tab_set_word_kernel(uint64_t *dst, uint64_t v) { *dst = v; }
-__global__ void tab_add_word_kernel(uint64_t *dst, uint64_t d) { *dst += d; }
-
 struct TabResetArgs {
     int32_t *state, *elapsed;
     const uint64_t *seeds;
@@ -452,12 +447,11 @@ __global__ void __launch_bounds__(kTabBlock) tab_reset_kernel(TabResetArgs a) {
 
 }  // namespace
 
-struct mxv_tab {
+struct mxv_tab : mxv::HostCore {
+    static constexpr const char *kNullMessage = "NULL mxv_tab";
+    mxv_tab() : HostCore("mxv_tab") {}
     mxv_tab_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int32_t *state = nullptr, *elapsed = nullptr, *err = nullptr, *nt = nullptr;
-    uint64_t *seeds = nullptr;
+    int32_t *state = nullptr, *elapsed = nullptr, *nt = nullptr;
     double *cum = nullptr, *prob = nullptr, *reward = nullptr, *init_cum = nullptr;
     size_t lds_bytes = 0;
     bool lds_table = false;
@@ -467,15 +461,7 @@ struct mxv_tab {
     int last_kernel = MXV_TAB_KERNEL_NONE;
     int log2S = 0;
     int single_start = -1;
-    uint64_t base_seed = 0, action_seed = 0, t = 0;
-    uint64_t *t_dev = nullptr;   // device clock (mxv_tab_set_device_clock)
-    bool dev_clock = false;
-    uint32_t r = 0;
-    bool was_reset = false;
-    // episode statistics (mxv_tab_episode_stats): running returns, the caller's trajectory outputs, dense staging of host steps
-    float *ep_acc = nullptr, *ep_return_out = nullptr, *st_ep_r = nullptr;
-    int32_t *ep_length_out = nullptr, *st_ep_l = nullptr;
-    bool ep_host_step = false;   // the launch in flight is a host step: its statistics go to the staging arrays
+    bool ep_host_step = false;   // the launch in flight is a host step: its episode statistics go to the staging arrays
     // staging for *_host calls
     int64_t *st_actions = nullptr, *st_obs = nullptr, *st_final = nullptr;
     double *st_reward = nullptr, *st_prob = nullptr, *st_fprob = nullptr, *st_uniforms = nullptr;
@@ -486,68 +472,20 @@ struct mxv_tab {
     char *hm_block = nullptr;
     int32_t *hm_err = nullptr;
     bool hostmap = false, err_in_block = false;
-    std::string error;
 };
 
 namespace {
 
-thread_local std::string g_tab_create_error;
-
-int tfail(mxv_tab *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h)
-        h->error = buf;
-    else
-        g_tab_create_error = buf;
-    return code;
-}
-
-#define TAB_HIP(h, expr)                                                                             \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return tfail((h), MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-#define TAB_CHECK(h) \
-    if (!(h)) return tfail(nullptr, MXV_ERR_INVALID_ARG, "NULL mxv_tab")
-
-// see mxv_set_device_clock (include/mxv.h): the step index on the device, advanced on the stream
-int tab_clock_add(mxv_tab *h, int64_t delta) {
-    h->t += (uint64_t)delta;
-    if (h->dev_clock) {
-        hipLaunchKernelGGL(tab_add_word_kernel, dim3(1), dim3(1), 0, h->stream, h->t_dev, (uint64_t)delta);
-        TAB_HIP(h, hipGetLastError());
-    }
-    return MXV_OK;
-}
-int tab_clock_set(mxv_tab *h) {
-    if (h->dev_clock) {
-        hipLaunchKernelGGL(tab_set_word_kernel, dim3(1), dim3(1), 0, h->stream, h->t_dev, h->t);
-        TAB_HIP(h, hipGetLastError());
-    }
-    return MXV_OK;
+int invalid_action(mxv_tab *h) {
+    return fail(h, MXV_ERR_INVALID_ACTION, "discrete action outside [0, %d) (Discrete.contains)", h->cfg.num_actions);
 }
 
 int tab_check_latched(mxv_tab *h) {
     int32_t e = 0;
-    TAB_HIP(h, hipMemcpyAsync(&e, h->err, sizeof e, hipMemcpyDeviceToHost, h->stream));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    if (e != 0) {
-        TAB_HIP(h, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
-        return tfail(h, MXV_ERR_INVALID_ACTION, "discrete action outside [0, %d) (Discrete.contains)", h->cfg.num_actions);
-    }
-    return MXV_OK;
+    if (int rc = take_latched(h, &e)) return rc;
+    return e != 0 ? invalid_action(h) : MXV_OK;
 }
 
-// caller-owned tensors on their element's natural boundary (see check_aligned in mxv_api.cpp): refused by name, not torn
-int tab_aligned(mxv_tab *h, const void *p, size_t bytes, const char *what) {
-    if (p && ((uintptr_t)p & (bytes - 1)) != 0) return tfail(h, MXV_ERR_INVALID_ARG, "%s pointer %p is not %zu-byte aligned", what, p, bytes);
-    return MXV_OK;
-}
 int tab_check_buffers(mxv_tab *h, bool compact, const void *actions, const void *actions_out, const void *uniforms, const void *obs,
                       const void *reward, const void *prob, const void *final_obs, const void *final_prob) {
     const size_t w = compact ? 4 : 8;
@@ -556,7 +494,7 @@ int tab_check_buffers(mxv_tab *h, bool compact, const void *actions, const void 
         {prob, w, "prob"}, {final_obs, w, "final_obs"}, {final_prob, w, "final_prob"}, {h->ep_return_out, 4, "episode return"},
         {h->ep_length_out, 4, "episode length"}};
     for (const auto &e : t)
-        if (int rc = tab_aligned(h, e.p, e.b, e.what)) return rc;
+        if (int rc = check_aligned(h, e.p, e.b, e.what)) return rc;
     return MXV_OK;
 }
 
@@ -564,11 +502,11 @@ int tab_launch(mxv_tab *h, int K, int64_t slice, const void *actions, int64_t ac
                const double *uniforms, void *obs, void *reward, uint8_t *term, uint8_t *trunc, void *prob,
                void *final_obs, void *final_prob, bool compact = false) {
     if (!h->was_reset)
-        return tfail(h, MXV_ERR_RESET_NEEDED, "Cannot call step before calling reset (gym.error.ResetNeeded)");
-    if (!obs) return tfail(h, MXV_ERR_INVALID_ARG, "obs pointer is NULL");
-    if (K <= 0) return tfail(h, MXV_ERR_INVALID_ARG, "K must be positive");
+        return fail(h, MXV_ERR_RESET_NEEDED, "Cannot call step before calling reset (gym.error.ResetNeeded)");
+    if (!obs) return fail(h, MXV_ERR_INVALID_ARG, "obs pointer is NULL");
+    if (K <= 0) return fail(h, MXV_ERR_INVALID_ARG, "K must be positive");
     if (int rc = tab_check_buffers(h, compact, actions, actions_out, uniforms, obs, reward, prob, final_obs, final_prob)) return rc;
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     TabArgs a{};
     a.state = h->state; a.elapsed = h->elapsed; a.seeds = h->seeds;
     a.cum = h->cum; a.prob = h->prob; a.reward = h->reward; a.nt = h->nt; a.init_cum = h->init_cum;
@@ -595,11 +533,10 @@ int tab_launch(mxv_tab *h, int K, int64_t slice, const void *actions, int64_t ac
         else
             hipLaunchKernelGGL((tab_step_kernel<false, false>), dim3(blocks), dim3(kTabBlock), 0, h->stream, a);
     }
-    TAB_HIP(h, hipGetLastError());
+    MXV_HIP(h, hipGetLastError());
     h->last_kernel = MXV_TAB_KERNEL_GENERAL;
-    return tab_clock_add(h, K);
+    return clock_add(h, K);
 }
-
 // T = ceil(cum * 2^32 - 0.5) clamped to [0, 2^32]: cum > (w + 0.5) * 2^-32  <=>  w < T for every 32-bit word w (both sides of the
 // rewrite are exact in fp64: cum * 2^32 is a scaling, the subtraction of 0.5 from a value below 2^33 loses nothing).
 uint64_t word_threshold(double cum) {
@@ -694,11 +631,12 @@ void launch_traj(mxv_tab *h, const TabTrajArgs &a0) {
     }
 }
 
+
 int tab_launch_traj(mxv_tab *h, int K, void *actions_out, void *obs, void *reward, uint8_t *term, uint8_t *trunc, void *prob, bool compact) {
     if (!h->was_reset)
-        return tfail(h, MXV_ERR_RESET_NEEDED, "Cannot call step before calling reset (gym.error.ResetNeeded)");
+        return fail(h, MXV_ERR_RESET_NEEDED, "Cannot call step before calling reset (gym.error.ResetNeeded)");
     if (int rc = tab_check_buffers(h, compact, nullptr, actions_out, nullptr, obs, reward, prob, nullptr, nullptr)) return rc;
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     TabTrajArgs a{};
     a.state = h->state; a.elapsed = h->elapsed; a.seeds = h->seeds;
     a.table = h->fast_tbl; a.table_words = h->fast_words; a.A = h->cfg.num_actions; a.ent_off = h->fast_ent_off;
@@ -723,14 +661,14 @@ int tab_launch_traj(mxv_tab *h, int K, void *actions_out, void *obs, void *rewar
         case 6: launch_traj<3, true, false>(h, a); break;
         default: launch_traj<3, true, true>(h, a); break;
     }
-    TAB_HIP(h, hipGetLastError());
+    MXV_HIP(h, hipGetLastError());
     h->last_kernel = MXV_TAB_KERNEL_TRAJECTORY;
-    return tab_clock_add(h, K);
+    return clock_add(h, K);
 }
 
 int tab_do_reset(mxv_tab *h, const uint8_t *mask_dev, int64_t *obs_dev) {
-    if (int rc = tab_aligned(h, obs_dev, 8, "obs")) return rc;
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
+    if (int rc = check_aligned(h, obs_dev, 8, "obs")) return rc;
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     h->r += 1;
     TabResetArgs a{};
     a.state = h->state; a.elapsed = h->elapsed; a.seeds = h->seeds; a.mask = mask_dev; a.init_cum = h->init_cum;
@@ -739,7 +677,7 @@ int tab_do_reset(mxv_tab *h, const uint8_t *mask_dev, int64_t *obs_dev) {
     a.ep_acc = h->ep_acc;
     const unsigned blocks = (unsigned)((h->cfg.num_envs + kTabBlock - 1) / kTabBlock);
     hipLaunchKernelGGL(tab_reset_kernel, dim3(blocks), dim3(kTabBlock), 0, h->stream, a);
-    TAB_HIP(h, hipGetLastError());
+    MXV_HIP(h, hipGetLastError());
     h->was_reset = true;
     return MXV_OK;
 }
@@ -750,7 +688,7 @@ int tab_ensure_staging(mxv_tab *h) {
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b8 = up(n * 8), b1 = up(n), total = 6 * b8 + up(2 * n * 8) + 3 * b1 + 256;
     if (total <= (size_t)2 << 20) {
-        TAB_HIP(h, hipHostMalloc((void **)&h->hm_block, total, hipHostMallocDefault));
+        MXV_HIP(h, hipHostMalloc((void **)&h->hm_block, total, hipHostMallocDefault));
         char *p = h->hm_block;
         h->st_actions = (int64_t *)p; p += b8;
         h->st_obs = (int64_t *)p; p += b8;
@@ -767,16 +705,16 @@ int tab_ensure_staging(mxv_tab *h) {
         h->hostmap = true;
         return MXV_OK;
     }
-    TAB_HIP(h, hipMalloc((void **)&h->st_actions, n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_obs, n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_final, n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_reward, n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_prob, n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_fprob, n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_uniforms, 2 * n * 8));
-    TAB_HIP(h, hipMalloc((void **)&h->st_term, n));
-    TAB_HIP(h, hipMalloc((void **)&h->st_trunc, n));
-    TAB_HIP(h, hipMalloc((void **)&h->st_mask, n));
+    MXV_HIP(h, hipMalloc((void **)&h->st_actions, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_obs, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_final, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_reward, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_prob, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_fprob, n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_uniforms, 2 * n * 8));
+    MXV_HIP(h, hipMalloc((void **)&h->st_term, n));
+    MXV_HIP(h, hipMalloc((void **)&h->st_trunc, n));
+    MXV_HIP(h, hipMalloc((void **)&h->st_mask, n));
     return MXV_OK;
 }
 
@@ -787,29 +725,31 @@ extern "C" {
 int mxv_tab_create(const mxv_tab_config *cfg, const double *cum_prob_host, const double *prob_host,
                    const int32_t *next_state_host, const double *reward_host, const uint8_t *terminated_host,
                    const double *initial_cum_host, mxv_tab **out) {
-    if (!cfg || !out) return tfail(nullptr, MXV_ERR_INVALID_ARG, "NULL config or output pointer");
+    if (!cfg || !out) return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "NULL config or output pointer");
     *out = nullptr;
     if (!cum_prob_host || !prob_host || !next_state_host || !reward_host || !terminated_host || !initial_cum_host)
-        return tfail(nullptr, MXV_ERR_INVALID_ARG, "NULL table pointer");
+        return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "NULL table pointer");
     const int S = cfg->num_states, A = cfg->num_actions, M = cfg->max_transitions;
     if (S <= 0 || A <= 0 || M <= 0 || (int64_t)S * A * M > (1 << 26))
-        return tfail(nullptr, MXV_ERR_INVALID_ARG, "bad table dimensions S=%d A=%d M=%d", S, A, M);
-    if (cfg->num_envs <= 0) return tfail(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be positive");
+        return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "bad table dimensions S=%d A=%d M=%d", S, A, M);
+    if (cfg->num_envs <= 0) return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "num_envs must be positive");
     if (cfg->env_offset < 0 || cfg->env_offset % MXV_ENV_ALIGN != 0)
-        return tfail(nullptr, MXV_ERR_INVALID_ARG, "env_offset must be a non-negative multiple of %d", MXV_ENV_ALIGN);
+        return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "env_offset must be a non-negative multiple of %d", MXV_ENV_ALIGN);
     const size_t entries = (size_t)S * A * M;
     for (size_t i = 0; i < entries; ++i)
         if (next_state_host[i] < 0 || next_state_host[i] >= S)
-            return tfail(nullptr, MXV_ERR_INVALID_ARG, "next_state[%zu] = %d outside [0, %d)", i, next_state_host[i], S);
+            return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "next_state[%zu] = %d outside [0, %d)", i, next_state_host[i], S);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
-        return tfail(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
+        return fail<mxv_tab>(nullptr, MXV_ERR_HIP, "no HIP device available (%s): the engine has no CPU fallback",
                      e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (cfg->device < 0 || cfg->device >= ndev) return tfail(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", cfg->device);
+    if (cfg->device < 0 || cfg->device >= ndev) return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "device %d out of range", cfg->device);
     mxv_tab *h = new (std::nothrow) mxv_tab();
-    if (!h) return tfail(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
+    if (!h) return fail<mxv_tab>(nullptr, MXV_ERR_INVALID_ARG, "out of host memory");
     h->cfg = *cfg;
+    h->device = cfg->device;
+    h->num_envs = cfg->num_envs;
     h->base_seed = cfg->seed;
     h->action_seed = cfg->action_seed;
     while ((1 << h->log2S) < S) h->log2S += 1;
@@ -826,38 +766,28 @@ int mxv_tab_create(const mxv_tab_config *cfg, const double *cum_prob_host, const
     std::vector<int32_t> packed(entries);
     for (size_t i = 0; i < entries; ++i) packed[i] = next_state_host[i] | (terminated_host[i] ? (int32_t)0x80000000 : 0);
     const size_t n = (size_t)cfg->num_envs;
-#define TAB_CREATE_HIP(expr)                                                     \
-    do {                                                                         \
-        hipError_t e_ = (expr);                                                  \
-        if (e_ != hipSuccess) {                                                  \
-            tfail(nullptr, MXV_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-            mxv_tab_destroy(h);                                                  \
-            return MXV_ERR_HIP;                                                  \
-        }                                                                        \
-    } while (0)
-    TAB_CREATE_HIP(hipSetDevice(cfg->device));
-    TAB_CREATE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipSetDevice(cfg->device));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
-    TAB_CREATE_HIP(hipMalloc((void **)&h->state, n * sizeof(int32_t)));
-    TAB_CREATE_HIP(hipMalloc((void **)&h->elapsed, n * sizeof(int32_t)));
-    TAB_CREATE_HIP(hipMalloc((void **)&h->err, sizeof(int32_t)));
-    TAB_CREATE_HIP(hipMalloc((void **)&h->t_dev, sizeof(uint64_t)));
-    TAB_CREATE_HIP(hipMalloc((void **)&h->reward, entries * sizeof(double)));
-    TAB_CREATE_HIP(hipMalloc((void **)&h->nt, entries * sizeof(int32_t)));
-    TAB_CREATE_HIP(hipMalloc((void **)&h->init_cum, (size_t)S * sizeof(double)));
-    if (need_cum) TAB_CREATE_HIP(hipMalloc((void **)&h->cum, entries * sizeof(double)));
-    if (!all_one) TAB_CREATE_HIP(hipMalloc((void **)&h->prob, entries * sizeof(double)));
-    TAB_CREATE_HIP(hipMemsetAsync(h->state, 0, n * sizeof(int32_t), h->stream));
-    TAB_CREATE_HIP(hipMemsetAsync(h->elapsed, 0, n * sizeof(int32_t), h->stream));
-    TAB_CREATE_HIP(hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
-    TAB_CREATE_HIP(hipMemsetAsync(h->t_dev, 0, sizeof(uint64_t), h->stream));
-    TAB_CREATE_HIP(hipMemcpyAsync(h->reward, reward_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    TAB_CREATE_HIP(hipMemcpyAsync(h->nt, packed.data(), entries * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    TAB_CREATE_HIP(hipMemcpyAsync(h->init_cum, initial_cum_host, (size_t)S * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (need_cum) TAB_CREATE_HIP(hipMemcpyAsync(h->cum, cum_prob_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!all_one) TAB_CREATE_HIP(hipMemcpyAsync(h->prob, prob_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    TAB_CREATE_HIP(hipStreamSynchronize(h->stream));
-#undef TAB_CREATE_HIP
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->state, n * sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->elapsed, n * sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->err, sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->t_dev, sizeof(uint64_t)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->reward, entries * sizeof(double)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->nt, entries * sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->init_cum, (size_t)S * sizeof(double)));
+    if (need_cum) MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->cum, entries * sizeof(double)));
+    if (!all_one) MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->prob, entries * sizeof(double)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->state, 0, n * sizeof(int32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->elapsed, 0, n * sizeof(int32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->t_dev, 0, sizeof(uint64_t), h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->reward, reward_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->nt, packed.data(), entries * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->init_cum, initial_cum_host, (size_t)S * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (need_cum) MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->cum, cum_prob_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!all_one) MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->prob, prob_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, hipStreamSynchronize(h->stream));
     h->lds_bytes = entries * (sizeof(double) * (1 + (need_cum ? 1 : 0) + (all_one ? 0 : 1)) + sizeof(int32_t)) + (size_t)S * sizeof(double);
     h->lds_table = h->lds_bytes <= 64 * 1024;  // larger MDPs (custom maps) read the table through L2 instead
     if (!(cfg->flags & MXV_TAB_FLAG_GENERAL_KERNEL)) {
@@ -868,7 +798,7 @@ int mxv_tab_create(const mxv_tab_config *cfg, const double *cum_prob_host, const
             hipError_t e1 = hipMalloc((void **)&h->fast_tbl, w.size() * 4);
             if (e1 == hipSuccess) e1 = hipMemcpy(h->fast_tbl, w.data(), w.size() * 4, hipMemcpyHostToDevice);
             if (e1 != hipSuccess) {
-                tfail(nullptr, MXV_ERR_HIP, "packed transition table: %s", hipGetErrorString(e1));
+                fail<mxv_tab>(nullptr, MXV_ERR_HIP, "packed transition table: %s", hipGetErrorString(e1));
                 mxv_tab_destroy(h);
                 return MXV_ERR_HIP;
             }
@@ -882,12 +812,7 @@ int mxv_tab_create(const mxv_tab_config *cfg, const double *cum_prob_host, const
 
 int mxv_tab_destroy(mxv_tab *h) {
     if (!h) return MXV_OK;
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *bufs[] = {h->state, h->elapsed, h->err, h->nt, h->seeds, h->cum, h->prob, h->reward, h->init_cum, h->fast_tbl, h->t_dev,
-                    h->ep_acc, h->st_ep_r, h->st_ep_l};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
+    drain(h);
     if (h->hostmap) {
         (void)hipHostFree(h->hm_block);
     } else {
@@ -896,49 +821,34 @@ int mxv_tab_destroy(mxv_tab *h) {
         for (void *p : stage)
             if (p) (void)hipFree(p);
     }
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    free_core(h, {h->state, h->elapsed, h->nt, h->cum, h->prob, h->reward, h->init_cum, h->fast_tbl});
     delete h;
     return MXV_OK;
 }
 
-const char *mxv_tab_last_error(const mxv_tab *h) { return h ? h->error.c_str() : g_tab_create_error.c_str(); }
+const char *mxv_tab_last_error(const mxv_tab *h) { return last_error(h); }
 
 int mxv_tab_seed(mxv_tab *h, uint64_t base_seed, const uint64_t *per_env_seeds_host) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    h->base_seed = base_seed;
-    h->t = 0;
-    h->r = 0;
-    if (int rc = tab_clock_set(h)) return rc;
-    if (per_env_seeds_host) {
-        const size_t bytes = (size_t)h->cfg.num_envs * sizeof(uint64_t);
-        if (!h->seeds) TAB_HIP(h, hipMalloc((void **)&h->seeds, bytes));
-        TAB_HIP(h, hipMemcpyAsync(h->seeds, per_env_seeds_host, bytes, hipMemcpyHostToDevice, h->stream));
-        TAB_HIP(h, hipStreamSynchronize(h->stream));
-    } else if (h->seeds) {
-        TAB_HIP(h, hipFree(h->seeds));
-        h->seeds = nullptr;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return reseed(h, base_seed, per_env_seeds_host);
 }
 
 int mxv_tab_seed_actions(mxv_tab *h, uint64_t action_seed) {
-    TAB_CHECK(h);
+    MXV_CHECK(h);
     h->action_seed = action_seed;
     return MXV_OK;
 }
 
 int mxv_tab_reset(mxv_tab *h, const uint8_t *mask_dev, int64_t *obs_dev) {
-    TAB_CHECK(h);
+    MXV_CHECK(h);
     return tab_do_reset(h, mask_dev, obs_dev);
 }
 
 int mxv_tab_step(mxv_tab *h, const int64_t *actions_dev, const double *uniforms_dev, int64_t *obs_dev, double *reward_dev,
                  uint8_t *terminated_dev, uint8_t *truncated_dev, double *prob_dev, int64_t *final_obs_dev,
                  double *final_prob_dev) {
-    TAB_CHECK(h);
-    if (!actions_dev) return tfail(h, MXV_ERR_INVALID_ARG, "actions pointer is NULL (use mxv_tab_rollout for sampled actions)");
+    MXV_CHECK(h);
+    if (!actions_dev) return fail(h, MXV_ERR_INVALID_ARG, "actions pointer is NULL (use mxv_tab_rollout for sampled actions)");
     return tab_launch(h, 1, 0, actions_dev, 0, nullptr, uniforms_dev, obs_dev, reward_dev, terminated_dev, truncated_dev,
                       prob_dev, final_obs_dev, final_prob_dev);
 }
@@ -946,7 +856,7 @@ int mxv_tab_step(mxv_tab *h, const int64_t *actions_dev, const double *uniforms_
 int mxv_tab_rollout(mxv_tab *h, int32_t K, int32_t per_step, void *actions_out_dev, void *obs_dev, void *reward_dev,
                     uint8_t *terminated_dev, uint8_t *truncated_dev, void *prob_dev, void *final_obs_dev,
                     void *final_prob_dev) {
-    TAB_CHECK(h);
+    MXV_CHECK(h);
     const bool compact = (h->cfg.flags & MXV_TAB_FLAG_COMPACT) != 0;
     if (h->fast_M != 0 && per_step && K > 0 && actions_out_dev && obs_dev && reward_dev && terminated_dev && truncated_dev && prob_dev &&
         !final_obs_dev && !final_prob_dev)
@@ -958,38 +868,38 @@ int mxv_tab_rollout(mxv_tab *h, int32_t K, int32_t per_step, void *actions_out_d
 int mxv_tab_rollout_tape(mxv_tab *h, int32_t K, int32_t per_step, const void *actions_tape_dev, void *obs_dev,
                          void *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, void *prob_dev,
                          void *final_obs_dev, void *final_prob_dev) {
-    TAB_CHECK(h);
-    if (!actions_tape_dev) return tfail(h, MXV_ERR_INVALID_ARG, "actions tape pointer is NULL");
+    MXV_CHECK(h);
+    if (!actions_tape_dev) return fail(h, MXV_ERR_INVALID_ARG, "actions tape pointer is NULL");
     return tab_launch(h, K, per_step ? h->cfg.num_envs : 0, actions_tape_dev, h->cfg.num_envs, nullptr, nullptr, obs_dev,
                       reward_dev, terminated_dev, truncated_dev, prob_dev, final_obs_dev, final_prob_dev,
                       (h->cfg.flags & MXV_TAB_FLAG_COMPACT) != 0);
 }
 
 int mxv_tab_reset_host(mxv_tab *h, const uint8_t *mask_host, int64_t *obs_host) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_CHECK(h);
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = tab_ensure_staging(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
     if (h->hostmap) {
         if (mask_host) std::memcpy(h->st_mask, mask_host, n);
         if (int rc = tab_do_reset(h, mask_host ? h->st_mask : nullptr, obs_host ? h->st_obs : nullptr)) return rc;
-        TAB_HIP(h, hipStreamSynchronize(h->stream));
+        MXV_HIP(h, hipStreamSynchronize(h->stream));
         if (obs_host) std::memcpy(obs_host, h->st_obs, n * 8);
         return MXV_OK;
     }
-    if (mask_host) TAB_HIP(h, hipMemcpyAsync(h->st_mask, mask_host, n, hipMemcpyHostToDevice, h->stream));
+    if (mask_host) MXV_HIP(h, hipMemcpyAsync(h->st_mask, mask_host, n, hipMemcpyHostToDevice, h->stream));
     if (int rc = tab_do_reset(h, mask_host ? h->st_mask : nullptr, obs_host ? h->st_obs : nullptr)) return rc;
-    if (obs_host) TAB_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, n * 8, hipMemcpyDeviceToHost, h->stream));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
+    if (obs_host) MXV_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, n * 8, hipMemcpyDeviceToHost, h->stream));
+    MXV_HIP(h, hipStreamSynchronize(h->stream));
     return MXV_OK;
 }
 
 int mxv_tab_step_host(mxv_tab *h, const int64_t *actions_host, const double *uniforms_host, int64_t *obs_host,
                       double *reward_host, uint8_t *terminated_host, uint8_t *truncated_host, double *prob_host,
                       int64_t *final_obs_host, double *final_prob_host) {
-    TAB_CHECK(h);
-    if (!actions_host || !obs_host) return tfail(h, MXV_ERR_INVALID_ARG, "actions/obs pointer is NULL");
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_CHECK(h);
+    if (!actions_host || !obs_host) return fail(h, MXV_ERR_INVALID_ARG, "actions/obs pointer is NULL");
+    MXV_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = tab_ensure_staging(h)) return rc;
     const size_t n = (size_t)h->cfg.num_envs;
     if (h->hostmap) {
@@ -1004,7 +914,7 @@ int mxv_tab_step_host(mxv_tab *h, const int64_t *actions_host, const double *uni
         h->err_in_block = false;
         h->ep_host_step = false;
         if (lrc) return lrc;
-        TAB_HIP(h, hipStreamSynchronize(h->stream));
+        MXV_HIP(h, hipStreamSynchronize(h->stream));
         std::memcpy(obs_host, h->st_obs, n * 8);
         if (reward_host) std::memcpy(reward_host, h->st_reward, n * 8);
         if (terminated_host) std::memcpy(terminated_host, h->st_term, n);
@@ -1014,13 +924,13 @@ int mxv_tab_step_host(mxv_tab *h, const int64_t *actions_host, const double *uni
         if (final_prob_host) std::memcpy(final_prob_host, h->st_fprob, n * 8);
         if (*h->hm_err != 0) {
             *h->hm_err = 0;
-            (void)tab_clock_add(h, -1);
-            return tfail(h, MXV_ERR_INVALID_ACTION, "discrete action outside [0, %d) (Discrete.contains)", h->cfg.num_actions);
+            (void)clock_add(h, -1);
+            return invalid_action(h);
         }
         return MXV_OK;
     }
-    TAB_HIP(h, hipMemcpyAsync(h->st_actions, actions_host, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (uniforms_host) TAB_HIP(h, hipMemcpyAsync(h->st_uniforms, uniforms_host, 2 * n * 8, hipMemcpyHostToDevice, h->stream));
+    MXV_HIP(h, hipMemcpyAsync(h->st_actions, actions_host, n * 8, hipMemcpyHostToDevice, h->stream));
+    if (uniforms_host) MXV_HIP(h, hipMemcpyAsync(h->st_uniforms, uniforms_host, 2 * n * 8, hipMemcpyHostToDevice, h->stream));
     h->ep_host_step = true;
     const int lrc = tab_launch(h, 1, 0, h->st_actions, 0, nullptr, uniforms_host ? h->st_uniforms : nullptr, h->st_obs,
                                reward_host ? h->st_reward : nullptr, terminated_host ? h->st_term : nullptr,
@@ -1028,131 +938,66 @@ int mxv_tab_step_host(mxv_tab *h, const int64_t *actions_host, const double *uni
                                final_obs_host ? h->st_final : nullptr, final_prob_host ? h->st_fprob : nullptr);
     h->ep_host_step = false;
     if (lrc) return lrc;
-    TAB_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (reward_host) TAB_HIP(h, hipMemcpyAsync(reward_host, h->st_reward, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (terminated_host) TAB_HIP(h, hipMemcpyAsync(terminated_host, h->st_term, n, hipMemcpyDeviceToHost, h->stream));
-    if (truncated_host) TAB_HIP(h, hipMemcpyAsync(truncated_host, h->st_trunc, n, hipMemcpyDeviceToHost, h->stream));
-    if (prob_host) TAB_HIP(h, hipMemcpyAsync(prob_host, h->st_prob, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (final_obs_host) TAB_HIP(h, hipMemcpyAsync(final_obs_host, h->st_final, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (final_prob_host) TAB_HIP(h, hipMemcpyAsync(final_prob_host, h->st_fprob, n * 8, hipMemcpyDeviceToHost, h->stream));
+    MXV_HIP(h, hipMemcpyAsync(obs_host, h->st_obs, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (reward_host) MXV_HIP(h, hipMemcpyAsync(reward_host, h->st_reward, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (terminated_host) MXV_HIP(h, hipMemcpyAsync(terminated_host, h->st_term, n, hipMemcpyDeviceToHost, h->stream));
+    if (truncated_host) MXV_HIP(h, hipMemcpyAsync(truncated_host, h->st_trunc, n, hipMemcpyDeviceToHost, h->stream));
+    if (prob_host) MXV_HIP(h, hipMemcpyAsync(prob_host, h->st_prob, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (final_obs_host) MXV_HIP(h, hipMemcpyAsync(final_obs_host, h->st_final, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (final_prob_host) MXV_HIP(h, hipMemcpyAsync(final_prob_host, h->st_fprob, n * 8, hipMemcpyDeviceToHost, h->stream));
     int rc = tab_check_latched(h);
-    if (rc == MXV_ERR_INVALID_ACTION) (void)tab_clock_add(h, -1);
+    if (rc == MXV_ERR_INVALID_ACTION) (void)clock_add(h, -1);
     return rc;
 }
 
 /* gym.wrappers.RecordEpisodeStatistics fused into the step (record_episode_statistics.py:96-151): see mxv_toytext.h */
 int mxv_tab_episode_stats(mxv_tab *h, int32_t enable) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (enable && !h->ep_acc) {
-        TAB_HIP(h, hipMalloc((void **)&h->ep_acc, n * sizeof(float)));
-        TAB_HIP(h, hipMalloc((void **)&h->st_ep_r, n * sizeof(float)));
-        TAB_HIP(h, hipMalloc((void **)&h->st_ep_l, n * sizeof(int32_t)));
-        TAB_HIP(h, hipMemsetAsync(h->ep_acc, 0, n * sizeof(float), h->stream));
-        TAB_HIP(h, hipMemsetAsync(h->st_ep_r, 0, n * sizeof(float), h->stream));
-        TAB_HIP(h, hipMemsetAsync(h->st_ep_l, 0, n * sizeof(int32_t), h->stream));
-        TAB_HIP(h, hipStreamSynchronize(h->stream));
-    } else if (!enable && h->ep_acc) {
-        TAB_HIP(h, hipFree(h->ep_acc));
-        TAB_HIP(h, hipFree(h->st_ep_r));
-        TAB_HIP(h, hipFree(h->st_ep_l));
-        h->ep_acc = h->st_ep_r = nullptr;
-        h->st_ep_l = nullptr;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return episode_stats(h, enable);
 }
 
 int mxv_tab_set_episode_outputs(mxv_tab *h, float *ep_return_dev, int32_t *ep_length_dev) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    h->ep_return_out = ep_return_dev;
-    h->ep_length_out = ep_length_dev;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_episode_outputs(h, ep_return_dev, ep_length_dev);
 }
 
 int mxv_tab_episode_stats_host(mxv_tab *h, float *ep_return_host, int32_t *ep_length_host, float *running_return_host) {
-    TAB_CHECK(h);
-    if (!h->ep_acc) return tfail(h, MXV_ERR_INVALID_ARG, "episode statistics are not enabled (mxv_tab_episode_stats)");
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (ep_return_host) TAB_HIP(h, hipMemcpyAsync(ep_return_host, h->st_ep_r, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (ep_length_host) TAB_HIP(h, hipMemcpyAsync(ep_length_host, h->st_ep_l, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (running_return_host) TAB_HIP(h, hipMemcpyAsync(running_return_host, h->ep_acc, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return episode_stats_host(h, ep_return_host, ep_length_host, running_return_host);
 }
 
 int mxv_tab_set_running_returns(mxv_tab *h, const float *running_return_host) {
-    TAB_CHECK(h);
-    if (!h->ep_acc) return tfail(h, MXV_ERR_INVALID_ARG, "episode statistics are not enabled (mxv_tab_episode_stats)");
-    if (!running_return_host) return tfail(h, MXV_ERR_INVALID_ARG, "NULL pointer");
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    TAB_HIP(h, hipMemcpyAsync(h->ep_acc, running_return_host, (size_t)h->cfg.num_envs * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_running_returns(h, running_return_host);
 }
 
 int mxv_tab_get_state(mxv_tab *h, int32_t *state_host, int32_t *elapsed_host) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (state_host) TAB_HIP(h, hipMemcpyAsync(state_host, h->state, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (elapsed_host) TAB_HIP(h, hipMemcpyAsync(elapsed_host, h->elapsed, n * 4, hipMemcpyDeviceToHost, h->stream));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    return MXV_OK;
+    MXV_CHECK(h);
+    return read_state32(h, h->state, h->elapsed, state_host, elapsed_host);
 }
 
 int mxv_tab_set_state(mxv_tab *h, const int32_t *state_host, const int32_t *elapsed_host) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    const size_t n = (size_t)h->cfg.num_envs;
-    if (state_host) {
-        for (size_t i = 0; i < n; ++i)
+    MXV_CHECK(h);
+    if (state_host)
+        for (int64_t i = 0; i < h->cfg.num_envs; ++i)
             if (state_host[i] < 0 || state_host[i] >= h->cfg.num_states)
-                return tfail(h, MXV_ERR_INVALID_ARG, "state[%zu] = %d outside [0, %d)", i, state_host[i], h->cfg.num_states);
-        TAB_HIP(h, hipMemcpyAsync(h->state, state_host, n * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (elapsed_host) TAB_HIP(h, hipMemcpyAsync(h->elapsed, elapsed_host, n * 4, hipMemcpyHostToDevice, h->stream));
-    TAB_HIP(h, hipStreamSynchronize(h->stream));
-    h->was_reset = true;
-    return MXV_OK;
+                return fail(h, MXV_ERR_INVALID_ARG, "state[%zu] = %d outside [0, %d)", (size_t)i, state_host[i], h->cfg.num_states);
+    return write_state32(h, h->state, h->elapsed, state_host, elapsed_host);
 }
 
 int mxv_tab_get_counters(mxv_tab *h, uint64_t *t, uint32_t *r) {
-    TAB_CHECK(h);
-    if (h->dev_clock) {  // a caller's graph replays advance the device word only
-        TAB_HIP(h, hipSetDevice(h->cfg.device));
-        TAB_HIP(h, hipMemcpyAsync(&h->t, h->t_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        TAB_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (t) *t = h->t;
-    if (r) *r = h->r;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return get_counters(h, t, r);
 }
 
 int mxv_tab_set_counters(mxv_tab *h, uint64_t t, uint32_t r) {
-    TAB_CHECK(h);
-    h->t = t;
-    h->r = r;
-    return tab_clock_set(h);
+    MXV_CHECK(h);
+    return set_counters(h, t, r);
 }
 
 int mxv_tab_set_device_clock(mxv_tab *h, int32_t on) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    if (on && !h->dev_clock) {
-        h->dev_clock = true;
-        return tab_clock_set(h);
-    }
-    if (!on && h->dev_clock) {
-        TAB_HIP(h, hipMemcpyAsync(&h->t, h->t_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        TAB_HIP(h, hipStreamSynchronize(h->stream));
-        h->dev_clock = false;
-    }
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_device_clock(h, on);
 }
 
 uint64_t mxv_tab_word_threshold(double cum_prob) { return word_threshold(cum_prob); }
@@ -1160,19 +1005,14 @@ uint64_t mxv_tab_word_threshold(double cum_prob) { return word_threshold(cum_pro
 int mxv_tab_last_kernel(const mxv_tab *h) { return h ? h->last_kernel : MXV_TAB_KERNEL_NONE; }
 
 int mxv_tab_sync(mxv_tab *h) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
+    MXV_CHECK(h);
+    if (int rc = use_device(h)) return rc;
     return tab_check_latched(h);
 }
 
 int mxv_tab_set_stream(mxv_tab *h, void *stream) {
-    TAB_CHECK(h);
-    TAB_HIP(h, hipSetDevice(h->cfg.device));
-    if (h->stream) TAB_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->own_stream && h->stream) TAB_HIP(h, hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return MXV_OK;
+    MXV_CHECK(h);
+    return set_stream(h, stream);
 }
 
 }  // extern "C"
