@@ -15,6 +15,7 @@ _LAZY = {
     "make": ("gym_amd.vector_env", "make"),
     "HipEnv": ("gym_amd.single_env", "HipEnv"),
     "DeviceRollout": ("gym_amd.rollout", "DeviceRollout"),
+    "PixelRollout": ("gym_amd.pixels", "PixelRollout"),
     "ShardedRollout": ("gym_amd.distributed", "ShardedRollout"),
     "MixedRollout": ("gym_amd.mixed", "MixedRollout"),
     "RecordEpisodeStatistics": ("gym_amd.wrappers", "RecordEpisodeStatistics"),

@@ -1,4 +1,5 @@
-"""ctypes binding of include/mxv_render.h: rgb_array frames of the classic-control envs, drawn on the device.
+"""ctypes binding of include/mxv_render.h: rgb_array frames of the classic-control envs, drawn on the device, and the
+pixel observations reduced from them.
 
 The header is optional (mxv.h does not include it), so its symbols are bound here, over the same library as gym_amd._native, and are
 not part of _native.EXPORTS.
@@ -11,7 +12,8 @@ import numpy as np
 
 from . import _native
 
-RENDER_EXPORTS = ("mxv_render_dims", "mxv_render", "mxv_render_host", "mxv_render_scene_host")
+RENDER_EXPORTS = ("mxv_render_dims", "mxv_render", "mxv_render_host", "mxv_render_scene_host", "mxv_pixels", "mxv_pixels_strided",
+                  "mxv_pixels_host")
 RECORD_INTS = 12
 MAX_RECORDS = 112
 # frames per second of the reference's metadata (cartpole.py:89, acrobot.py:96, mountain_car.py:100, continuous_mountain_car.py:105)
@@ -24,6 +26,9 @@ lib.mxv_render_dims.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_i
 lib.mxv_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.mxv_render_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
 lib.mxv_render_scene_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+lib.mxv_pixels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+lib.mxv_pixels_strided.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64]
+lib.mxv_pixels_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
 for _name in RENDER_EXPORTS:
     getattr(lib, _name).restype = C.c_int
 
@@ -73,3 +78,41 @@ def render_device(handle, frames, indices=None, count=None):
     handle's stream, no synchronisation."""
     k = int(count if count is not None else (indices.numel() if indices is not None else handle.num_envs))
     handle._check(lib.mxv_render(handle._h, None if indices is None else indices.data_ptr(), k, frames.data_ptr()))
+
+
+def pixel_shape(env_id: int, height: int, width: int, grayscale: bool):
+    """Shape of one pixel observation: (height, width) or (height, width, 3).  NotImplementedError for Pendulum, ValueError for a size
+    outside [1, H] x [1, W] of the kind's frame."""
+    H, W = dims(env_id)
+    if not (isinstance(height, int) and isinstance(width, int) and 1 <= height <= H and 1 <= width <= W):
+        raise ValueError(f"pixel observations are reduced from the {H} x {W} frame: height must lie in [1, {H}] and width in [1, {W}], "
+                         f"got {height!r} x {width!r}")
+    return (height, width) if grayscale else (height, width, 3)
+
+
+def pixels_host(handle, height: int, width: int, grayscale: bool = True, indices=None) -> np.ndarray:
+    """uint8 (k, h, w) or (k, h, w, 3) pixel observations of envs `indices` (all when None) in host memory.  Synchronises."""
+    shape = pixel_shape(handle.env_id, height, width, grayscale)
+    idx, k = _indices_host(handle, indices)
+    out = np.empty((k,) + shape, np.uint8)
+    if k == 0:
+        return out
+    handle._check(lib.mxv_pixels_host(handle._h, None if idx is None else idx.ctypes.data, k, height, width, 1 if grayscale else 3,
+                                      out.ctypes.data))
+    return out
+
+
+def pixels_device(handle, out, height: int, width: int, grayscale: bool = True, indices=None, count=None):
+    """Pixel observations into the device tensor `out` (uint8 [count, h, w(, 3)]); `indices` an int32 device tensor or None.
+    Stream-ordered on the handle's stream, no synchronisation."""
+    k = int(count if count is not None else (indices.numel() if indices is not None else handle.num_envs))
+    handle._check(lib.mxv_pixels(handle._h, None if indices is None else indices.data_ptr(), k, height, width, 1 if grayscale else 3,
+                                 out.data_ptr()))
+
+
+def pixels_strided(handle, out_ptr: int, height: int, width: int, grayscale: bool, copies: int, env_stride: int, copy_stride: int,
+                   mask=None):
+    """Every env i whose mask byte is set (all when `mask` is None; a uint8 device tensor [N]): its observation `copies` times at
+    out_ptr + i * env_stride + c * copy_stride (bytes).  Stream-ordered on the handle's stream, no synchronisation."""
+    handle._check(lib.mxv_pixels_strided(handle._h, None if mask is None else mask.data_ptr(), height, width, 1 if grayscale else 3,
+                                         int(copies), out_ptr, int(env_stride), int(copy_stride)))

@@ -1712,6 +1712,8 @@ int render_view(mxv_handle *h, RenderView *v) {
     return MXV_OK;
 }
 
+int32_t render_env_id(const mxv_handle *h) { return h->cfg.env_id; }
+
 int render_fail(mxv_handle *h, int code, const char *message) { return fail(h, code, "%s", message); }
 
 }  // namespace mxv

@@ -11,8 +11,12 @@
 // kept), and writes the band as a flat byte stream: a thread owns runs of 16 pixels = 48 B = 3 dwordx4 stores (runs may straddle rows;
 // 16 rows x W pixels is a whole number of runs, and every frame is a multiple of 16 B).  A band no record reaches is all white: stores
 // only.  Envs whose index lies outside [0, N) get an all-zero frame and latch kRenderIndexErrorBit.
+//
+// pixels_kernel (below) draws the same pixels into LDS and reduces them to pixel observations (gray, area resize) without writing the
+// frame (DESIGN.md §10 "Pixel observations").
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -417,16 +421,93 @@ __device__ inline void store_run(uint4 *dst, uint32_t word) {
     dst[2] = v;
 }
 
+// A workgroup's view of its scene's records: clipped pixel bounding boxes and the list of those that reach its rows, in draw order.
+struct CullLds {
+    int32_t bbox[kMaxRec][4];
+    int32_t list[kMaxRec];
+    uint64_t masks[kMaxRec / 64 + 1];
+    int32_t nlist;
+};
+
+// The records whose bounding box (C.bbox, filled by threads t < kMaxRec) reaches surface rows [ylo, yhi], ballot-compacted into C.list
+// in draw order; returns their number.  Called by every thread; ends with a barrier.
+__device__ inline int cull_records(CullLds &C, int ylo, int yhi) {
+    const int t = threadIdx.x;
+    bool hit = false;
+    if (t < kMaxRec) {
+        const int32_t *b = C.bbox[t];
+        hit = b[0] <= b[1] && b[2] <= b[3] && b[3] >= ylo && b[2] <= yhi;
+    }
+    const uint64_t ballot = __ballot(hit);
+    const int wave = t / 64, lane = t % 64;
+    if (lane == 0 && wave <= kMaxRec / 64) C.masks[wave] = ballot;
+    __syncthreads();
+    if (hit) {
+        int pos = __popcll(ballot & ((1ull << lane) - 1));
+        for (int w = 0; w < wave; ++w) pos += __popcll(C.masks[w]);
+        C.list[pos] = t;
+    }
+    if (t == 0) {
+        int total = 0;
+        for (int w = 0; w <= kMaxRec / 64; ++w) total += __popcll(C.masks[w]);
+        C.nlist = total;
+    }
+    __syncthreads();
+    return C.nlist;
+}
+
+// The listed records whose box reaches columns [rx0, rx1] of surface rows [yB, yA] (a run of 16 pixels), as a bit set over the list.
+__device__ inline void run_candidates(const CullLds &C, int nl, int rx0, int rx1, int yB, int yA, uint64_t *cand0, uint64_t *cand1) {
+    uint64_t c0 = 0, c1 = 0;
+    for (int li = 0; li < nl; ++li) {
+        const int k = C.list[li];
+        if (C.bbox[k][1] < rx0 || C.bbox[k][0] > rx1 || C.bbox[k][3] < yB || C.bbox[k][2] > yA) continue;
+        if (li < 64)
+            c0 |= 1ull << li;
+        else
+            c1 |= 1ull << (li - 64);
+    }
+    *cand0 = c0;
+    *cand1 = c1;
+}
+
+// The colour 0xRRGGBB of surface pixel (x, y): white, then every candidate record that covers samples of it blended in draw order.
+__device__ inline uint32_t shade(const SceneLds &L, const CullLds &C, uint64_t cand0, uint64_t cand1, int x, int y) {
+    uint32_t cr = 255, cg = 255, cb = 255;
+    for (int h = 0; h < 2; ++h)
+    for (uint64_t mm = h ? cand1 : cand0; mm; mm &= mm - 1) {
+        const int k = C.list[h * 64 + __ffsll((unsigned long long)mm) - 1];
+        if (x < C.bbox[k][0] || x > C.bbox[k][1] || y < C.bbox[k][2] || y > C.bbox[k][3]) continue;
+        const int32_t *r = L.rec[k];
+        const int c = coverage(r, x, y);
+        if (c == 0) continue;
+        const uint32_t rgb = (uint32_t)r[1], o = 16 - c;
+        cr = (cr * o + ((rgb >> 16) & 255) * c + 8) >> 4;
+        cg = (cg * o + ((rgb >> 8) & 255) * c + 8) >> 4;
+        cb = (cb * o + (rgb & 255) * c + 8) >> 4;
+    }
+    return cr << 16 | cg << 8 | cb;
+}
+
+// Surface rows [yB, yA] and columns [rx0, rx1] that bound the run of 16 pixels starting at flat pixel p0 of a block of rows that starts
+// at output row row0 (a run may straddle two rows: then it spans every column of both).
+__device__ inline void run_bounds(int H, int W, int row0, int p0, int *colA, int *yA, int *yB, int *rx0, int *rx1) {
+    const int rowA = row0 + p0 / W;
+    *colA = p0 % W;
+    const bool straddle = *colA + 15 >= W;
+    *yA = H - 1 - rowA;
+    *yB = straddle ? *yA - 1 : *yA;
+    *rx0 = straddle ? 0 : *colA;
+    *rx1 = straddle ? W - 1 : *colA + 15;
+}
+
 template <int H, int W>
 __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
     constexpr int kBands = (H + kBandRows - 1) / kBandRows;
     constexpr int64_t kFrameBytes = (int64_t)H * W * 3;
     static_assert(kFrameBytes % 16 == 0 && (kBandRows * W) % 16 == 0 && ((H % kBandRows) * W) % 16 == 0, "runs of 16 px tile every band");
     __shared__ SceneLds L;
-    __shared__ int32_t bbox[kMaxRec][4];
-    __shared__ int32_t list[kMaxRec];
-    __shared__ uint64_t masks[kMaxRec / 64 + 1];
-    __shared__ int32_t nlist;
+    __shared__ CullLds C;
     __shared__ __attribute__((aligned(16))) uint8_t stage[kThreads][48];   // each thread's run of 16 pixels, as bytes
     const int64_t frame = blockIdx.x / kBands;
     const int band = (int)(blockIdx.x % kBands);
@@ -443,48 +524,17 @@ __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
     }
     build_scene(a.kind, s, P, L.rec, L.tx, L.ty);
     // records that reach this band's rows, in draw order (surface y of output row R is H - 1 - R)
-    const int ylo = H - row0 - rows, yhi = H - 1 - row0;
-    bool hit = false;
-    if (t < kMaxRec) {
-        record_bbox(L.rec[t], H, W, bbox[t]);
-        hit = bbox[t][0] <= bbox[t][1] && bbox[t][2] <= bbox[t][3] && bbox[t][3] >= ylo && bbox[t][2] <= yhi;
-    }
-    const uint64_t ballot = __ballot(hit);
-    const int wave = t / 64, lane = t % 64;
-    if (lane == 0 && wave <= kMaxRec / 64) masks[wave] = ballot;
-    __syncthreads();
-    if (hit) {
-        int pos = __popcll(ballot & ((1ull << lane) - 1));
-        for (int w = 0; w < wave; ++w) pos += __popcll(masks[w]);
-        list[pos] = t;
-    }
-    if (t == 0) {
-        int total = 0;
-        for (int w = 0; w <= kMaxRec / 64; ++w) total += __popcll(masks[w]);
-        nlist = total;
-    }
-    __syncthreads();
-    const int nl = nlist;
+    if (t < kMaxRec) record_bbox(L.rec[t], H, W, C.bbox[t]);
+    const int nl = cull_records(C, H - row0 - rows, H - 1 - row0);
     if (nl == 0) {  // no primitive reaches these rows: white
         for (int run = t; run < runs; run += kThreads) store_run(o4 + 3 * run, 0xFFFFFFFFu);
         return;
     }
     for (int run = t; run < runs; run += kThreads) {
-        const int p0 = run * 16;
-        const int rowA = row0 + p0 / W, colA = p0 % W;
-        const bool straddle = colA + 15 >= W;
-        const int yA = H - 1 - rowA, yB = straddle ? yA - 1 : yA;
-        const int rx0 = straddle ? 0 : colA, rx1 = straddle ? W - 1 : colA + 15;
-        // the band's records that reach this run, as a bit set over the (ordered) list
-        uint64_t cand0 = 0, cand1 = 0;
-        for (int li = 0; li < nl; ++li) {
-            const int k = list[li];
-            if (bbox[k][1] < rx0 || bbox[k][0] > rx1 || bbox[k][3] < yB || bbox[k][2] > yA) continue;
-            if (li < 64)
-                cand0 |= 1ull << li;
-            else
-                cand1 |= 1ull << (li - 64);
-        }
+        int colA, yA, yB, rx0, rx1;
+        run_bounds(H, W, row0, run * 16, &colA, &yA, &yB, &rx0, &rx1);
+        uint64_t cand0, cand1;
+        run_candidates(C, nl, rx0, rx1, yB, yA, &cand0, &cand1);
         uint4 *d = o4 + 3 * run;
         if (!(cand0 | cand1)) {
             store_run(d, 0xFFFFFFFFu);
@@ -495,22 +545,10 @@ __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
         for (int j = 0; j < 16; ++j) {
             int x = colA + j, y = yA;
             if (x >= W) x -= W, y -= 1;
-            uint32_t cr = 255, cg = 255, cb = 255;
-            for (int h = 0; h < 2; ++h)
-            for (uint64_t mm = h ? cand1 : cand0; mm; mm &= mm - 1) {
-                const int k = list[h * 64 + __ffsll((unsigned long long)mm) - 1];
-                if (x < bbox[k][0] || x > bbox[k][1] || y < bbox[k][2] || y > bbox[k][3]) continue;
-                const int32_t *r = L.rec[k];
-                const int c = coverage(r, x, y);
-                if (c == 0) continue;
-                const uint32_t rgb = (uint32_t)r[1], o = 16 - c;
-                cr = (cr * o + ((rgb >> 16) & 255) * c + 8) >> 4;
-                cg = (cg * o + ((rgb >> 8) & 255) * c + 8) >> 4;
-                cb = (cb * o + (rgb & 255) * c + 8) >> 4;
-            }
-            mine[3 * j] = (uint8_t)cr;
-            mine[3 * j + 1] = (uint8_t)cg;
-            mine[3 * j + 2] = (uint8_t)cb;
+            const uint32_t c = shade(L, C, cand0, cand1, x, y);
+            mine[3 * j] = (uint8_t)(c >> 16);
+            mine[3 * j + 1] = (uint8_t)(c >> 8);
+            mine[3 * j + 2] = (uint8_t)c;
         }
         const uint4 *src = (const uint4 *)mine;
         d[0] = src[0];
@@ -519,18 +557,161 @@ __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
     }
 }
 
-int launch(const RenderView &v, const int32_t *idx_dev, int64_t count, uint8_t *frames, int32_t *records) {
+// -- pixel observations: render -> gray -> area resize in one pass (include/mxv_render.h mxv_pixels*, tests/pixels_host.py) --------
+constexpr int kMaxOutRow = 600 * 3;       // bytes of one output row at most (w <= W, channels <= 3)
+constexpr int kMaxBandBytes = 4 * kMaxOutRow;   // output bytes of one workgroup at most (its LDS stage)
+
+// Source rows one LDS tile holds: RGB triplets 16 rows (28.8 KB at W = 600, three workgroups per CU); gray bytes 48 rows at W = 600
+// (28.8 KB: 84-row observations in bands of 8 rows, 11 scene builds per frame) and 32 at W = 500, where 84 output rows make bands of
+// 4 rows either way and the smaller tile keeps four workgroups per CU.
+__host__ __device__ constexpr int tile_rows(int C, int W) { return C == 3 ? 16 : W == 600 ? 48 : 32; }
+
+struct PixelArgs {
+    RenderArgs r;           // state, attributes, indices, error word, N, kind (frames / records unused)
+    const uint8_t *mask;    // [frames] or nullptr: frames whose byte is 0 are skipped
+    uint8_t *out;           // frame k, copy c at out + k * env_stride + c * copy_stride: uint8 [h][w][channels]
+    int64_t env_stride, copy_stride;
+    int32_t h, w, copies;
+    int32_t band_rows;      // output rows per workgroup
+    int32_t bands;          // workgroups per frame
+};
+
+template <int C>
+__device__ inline void tile_put(uint8_t *tile, int p, uint32_t rgb) {
+    if (C == 1) {
+        tile[p] = (uint8_t)((4899u * (rgb >> 16) + 9617u * ((rgb >> 8) & 255u) + 1868u * (rgb & 255u) + 8192u) >> 14);
+    } else {
+        tile[3 * p] = (uint8_t)(rgb >> 16);
+        tile[3 * p + 1] = (uint8_t)(rgb >> 8);
+        tile[3 * p + 2] = (uint8_t)rgb;
+    }
+}
+
+// The band's nb output bytes (src: the LDS stage, or nullptr for `fill` everywhere) into every copy of the frame: a thread owns runs of
+// 16 bytes, one dwordx4 store per copy where the destination is 16-byte aligned, byte stores elsewhere.
+__device__ inline void store_band(const PixelArgs &a, uint8_t *dst0, int nb, const uint8_t *src, uint8_t fill) {
+    const uint32_t f4 = fill * 0x01010101u;
+    for (int g = threadIdx.x; 16 * g < nb; g += kThreads) {
+        const int n = min(16, nb - 16 * g);
+        uint8_t *dst = dst0 + 16 * g;
+        for (int c = 0; c < a.copies; ++c, dst += a.copy_stride) {
+            if (n == 16 && ((uintptr_t)dst & 15) == 0)
+                *(uint4 *)dst = src ? *(const uint4 *)(src + 16 * g) : make_uint4(f4, f4, f4, f4);
+            else
+                for (int k = 0; k < n; ++k) dst[k] = src ? src[16 * g + k] : fill;
+        }
+    }
+}
+
+// One workgroup of 256 threads per (frame, band of a.band_rows output rows).  The band's source rows are rasterised exactly as
+// render_kernel draws them (run_bounds, run_candidates, shade), chunk by chunk into an LDS tile with gray already applied; then one
+// thread per output byte sums its source block (the rows of it inside the chunk) and the band leaves through an LDS stage in 16-byte
+// stores.  A band whose source rows no record reaches is white without coverage work, and so is every run of 16 source pixels that no
+// record's box reaches.  A band that needs more source rows than one tile holds (h < H / tile rows: then a band is one output row)
+// keeps its running sums in LDS between chunks.
+template <int H, int W, int C>
+__global__ __launch_bounds__(kThreads) void pixels_kernel(PixelArgs a) {
+    constexpr int kRows = tile_rows(C, W);
+    static_assert(W * C <= kMaxOutRow, "one output row must fit the running sums (acc) and a band of four rows the stage");
+    __shared__ SceneLds L;
+    __shared__ CullLds Cl;
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kRows * W * C];
+    __shared__ uint32_t acc[kMaxOutRow];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kMaxBandBytes];
+    const int64_t frame = blockIdx.x / a.bands;
+    const int band = (int)(blockIdx.x % a.bands);
+    if (a.mask && a.mask[frame] == 0) return;
+    const int t = threadIdx.x;
+    const int h = a.h, w = a.w, rowb = w * C;
+    const int i0 = band * a.band_rows, i1 = min(h, i0 + a.band_rows);
+    const int nb = (i1 - i0) * rowb;                               // the band's output bytes (<= kMaxBandBytes, checked by the launch)
+    uint8_t *dst0 = a.out + frame * a.env_stride + (int64_t)i0 * rowb;
+    double s[4], P[MXV_MAX_PARAMS];
+    if (!load_env(a.r, frame, s, P)) {
+        if (t == 0 && band == 0) atomicOr(a.r.err, kRenderIndexErrorBit);
+        store_band(a, dst0, nb, nullptr, 0);
+        return;
+    }
+    build_scene(a.r.kind, s, P, L.rec, L.tx, L.ty);
+    if (t < kMaxRec) record_bbox(L.rec[t], H, W, Cl.bbox[t]);
+    const int r0 = (int)((int64_t)i0 * H / h), r1 = (int)(((int64_t)i1 * H + h - 1) / h);   // the band's source rows [r0, r1)
+    const int chunks = (r1 - r0 + kRows - 1) / kRows;
+    for (int q = 0; q < chunks; ++q) {
+        const int s0 = r0 + q * kRows, s1 = min(r1, s0 + kRows);
+        __syncthreads();                                           // the previous chunk's readers of the tile and the list are done
+        const int nl = cull_records(Cl, H - s1, H - 1 - s0);
+        if (nl == 0 && chunks == 1) {                              // no primitive reaches the band's source rows: white
+            store_band(a, dst0, nb, nullptr, 255);
+            return;
+        }
+        const int npix = (s1 - s0) * W;
+        for (int run = t; 16 * run < npix; run += kThreads) {
+            const int p0 = run * 16, n = min(16, npix - p0);
+            int colA, yA, yB, rx0, rx1;
+            run_bounds(H, W, s0, p0, &colA, &yA, &yB, &rx0, &rx1);
+            uint64_t cand0 = 0, cand1 = 0;
+            if (nl) run_candidates(Cl, nl, rx0, rx1, yB, yA, &cand0, &cand1);
+            if (!(cand0 | cand1) && n == 16) {
+                const uint4 white = make_uint4(~0u, ~0u, ~0u, ~0u);
+#pragma unroll
+                for (int k = 0; k < C; ++k) ((uint4 *)(tile + C * p0))[k] = white;
+                continue;
+            }
+#pragma nounroll
+            for (int j = 0; j < n; ++j) {
+                int x = colA + j, y = yA;
+                if (x >= W) x -= W, y -= 1;
+                tile_put<C>(tile, p0 + j, (cand0 | cand1) ? shade(L, Cl, cand0, cand1, x, y) : 0xFFFFFFu);
+            }
+        }
+        __syncthreads();
+        // output byte b: the sum over the rows of its source block inside this chunk; the rounded mean after the last chunk
+        for (int b = t; b < nb; b += kThreads) {
+            const int i = i0 + b / rowb, j = (b % rowb) / C, ch = b % C;
+            const int rlo = (int)((int64_t)i * H / h), rhi = (int)(((int64_t)(i + 1) * H + h - 1) / h);
+            const int clo = (int)((int64_t)j * W / w), chi = (int)(((int64_t)(j + 1) * W + w - 1) / w);
+            uint32_t sum = 0;
+            for (int rr = max(rlo, s0); rr < min(rhi, s1); ++rr) {
+                const uint8_t *row = tile + (rr - s0) * W * C + ch;
+                for (int cc = clo; cc < chi; ++cc) sum += row[cc * C];
+            }
+            if (chunks > 1) {                                      // one output row per band: nb <= kMaxOutRow
+                sum += q == 0 ? 0u : acc[b];
+                acc[b] = sum;
+            }
+            const uint32_t cnt = (uint32_t)(rhi - rlo) * (uint32_t)(chi - clo);
+            if (q + 1 == chunks) stage[b] = (uint8_t)((sum + cnt / 2) / cnt);
+        }
+    }
+    __syncthreads();
+    store_band(a, dst0, nb, stage, 0);
+}
+
+template <int H, int W>
+void launch_pixels_kind(const PixelArgs &a, int C, dim3 grid, hipStream_t stream) {
+    if (C == 1)
+        hipLaunchKernelGGL((pixels_kernel<H, W, 1>), grid, dim3(kThreads), 0, stream, a);
+    else
+        hipLaunchKernelGGL((pixels_kernel<H, W, 3>), grid, dim3(kThreads), 0, stream, a);
+}
+
+RenderArgs render_args(const RenderView &v, const int32_t *idx_dev) {
     RenderArgs a{};
     a.state = v.state;
     a.params_pe = v.params_pe;
     a.idx = idx_dev;
-    a.frames = frames;
-    a.records = records;
     a.err = v.err;
     a.n = v.n;
     a.kind = v.env_id;
     a.S = v.env_id == MXV_ACROBOT || v.env_id == MXV_CARTPOLE ? 4 : 2;
     std::memcpy(a.P, v.P, sizeof a.P);
+    return a;
+}
+
+int launch(const RenderView &v, const int32_t *idx_dev, int64_t count, uint8_t *frames, int32_t *records) {
+    RenderArgs a = render_args(v, idx_dev);
+    a.frames = frames;
+    a.records = records;
     if (records) {
         hipLaunchKernelGGL(scene_kernel, dim3((unsigned)count), dim3(kThreads), 0, v.stream, a);
     } else if (v.env_id == MXV_ACROBOT) {
@@ -540,6 +721,41 @@ int launch(const RenderView &v, const int32_t *idx_dev, int64_t count, uint8_t *
         hipLaunchKernelGGL((render_kernel<400, 600>), dim3((unsigned)(count * ((400 + kBandRows - 1) / kBandRows))), dim3(kThreads), 0,
                            v.stream, a);
     }
+    return hipGetLastError() == hipSuccess ? MXV_OK : MXV_ERR_HIP;
+}
+
+// Output rows per workgroup: as many as keep the band's source rows inside one tile (at least one) and its bytes inside the LDS stage,
+// rounded down to a multiple that starts every band on a 16-byte boundary of the frame where that still leaves one row or more.
+int pixel_band_rows(int H, int W, int h, int w, int C) {
+    const int rowb = w * C;
+    int R = std::max(1, (tile_rows(C, W) - 2) * h / H);
+    R = std::min(R, kMaxBandBytes / rowb);
+    int g = 16;
+    while (rowb % g) g /= 2;
+    const int align = 16 / g;
+    if (R >= align) R -= R % align;
+    return R;
+}
+
+int launch_pixels(const RenderView &v, const int32_t *idx_dev, const uint8_t *mask_dev, int64_t frames, int32_t height, int32_t width,
+                  int32_t channels, int32_t copies, uint8_t *out, int64_t env_stride, int64_t copy_stride) {
+    PixelArgs a{};
+    a.r = render_args(v, idx_dev);
+    a.mask = mask_dev;
+    a.out = out;
+    a.env_stride = env_stride;
+    a.copy_stride = copy_stride;
+    a.h = height;
+    a.w = width;
+    a.copies = copies;
+    const int H = frame_h(v.env_id);
+    a.band_rows = pixel_band_rows(H, frame_w(v.env_id), height, width, channels);
+    a.bands = (height + a.band_rows - 1) / a.band_rows;
+    const dim3 grid((unsigned)(frames * a.bands));
+    if (v.env_id == MXV_ACROBOT)
+        launch_pixels_kind<500, 500>(a, channels, grid, v.stream);
+    else
+        launch_pixels_kind<400, 600>(a, channels, grid, v.stream);
     return hipGetLastError() == hipSuccess ? MXV_OK : MXV_ERR_HIP;
 }
 
@@ -624,6 +840,77 @@ int mxv_render_host(mxv_handle *h, const int32_t *indices_host, int64_t count, u
 
 int mxv_render_scene_host(mxv_handle *h, const int32_t *indices_host, int64_t count, int32_t *records_host) {
     return render_to_host(h, indices_host, count, records_host, true);
+}
+
+// -- pixel observations ----------------------------------------------------------------------------------------------------------------
+// The kind, then the target size, channels and copies: before any device work.
+static int pixel_args(mxv_handle *h, int32_t height, int32_t width, int32_t channels, int32_t copies) {
+    const int32_t kind = render_env_id(h);
+    if (!renderable(kind))
+        return render_fail(h, MXV_ERR_UNSUPPORTED, "pixels: Pendulum-v1 draws an image asset (pendulum.py:228-244) that the engine does "
+                                                   "not carry: no frames for it");
+    if (channels != 1 && channels != 3) return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: channels must be 1 (gray) or 3 (RGB)");
+    if (height < 1 || height > frame_h(kind) || width < 1 || width > frame_w(kind))
+        return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: height / width must lie in [1, frame height / width]");
+    if (copies < 1) return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: copies must be >= 1");
+    return MXV_OK;
+}
+
+static int pixels_launch(mxv_handle *h, const RenderView &v, const int32_t *idx, const uint8_t *mask, int64_t frames, int32_t height,
+                         int32_t width, int32_t channels, int32_t copies, uint8_t *out, int64_t env_stride, int64_t copy_stride) {
+    const int rows = pixel_band_rows(frame_h(v.env_id), frame_w(v.env_id), height, width, channels), bands = (height + rows - 1) / rows;
+    if (frames * bands > (int64_t)UINT32_MAX / kThreads)
+        return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: too many frames for one launch at this size");
+    if (launch_pixels(v, idx, mask, frames, height, width, channels, copies, out, env_stride, copy_stride) != MXV_OK)
+        return render_fail(h, MXV_ERR_HIP, "pixels: kernel launch failed");
+    return MXV_OK;
+}
+
+int mxv_pixels(mxv_handle *h, const int32_t *indices_dev, int64_t count, int32_t height, int32_t width, int32_t channels,
+               uint8_t *out_dev) {
+    if (int rc = check_args(h, count, indices_dev != nullptr, out_dev)) return rc;
+    if ((uintptr_t)out_dev & 15) return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: output pointer is not 16-byte aligned");
+    if ((uintptr_t)indices_dev & 3) return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: index pointer is not 4-byte aligned");
+    if (int rc = pixel_args(h, height, width, channels, 1)) return rc;
+    RenderView v;
+    if (int rc = view_for(h, count, indices_dev != nullptr, &v)) return rc;
+    const int64_t frame = (int64_t)height * width * channels;
+    return pixels_launch(h, v, indices_dev, nullptr, count, height, width, channels, 1, out_dev, frame, 0);
+}
+
+int mxv_pixels_strided(mxv_handle *h, const uint8_t *mask_dev, int32_t height, int32_t width, int32_t channels, int32_t copies,
+                       uint8_t *out_dev, int64_t env_stride, int64_t copy_stride) {
+    if (!h) return MXV_ERR_INVALID_ARG;
+    if (!out_dev) return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: output pointer is NULL");
+    if (int rc = pixel_args(h, height, width, channels, copies)) return rc;
+    const int64_t frame = (int64_t)height * width * channels;
+    if (env_stride < frame || (copies > 1 && copy_stride < frame))
+        return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: env_stride (and copy_stride when copies > 1) must be >= height * width * channels");
+    RenderView v;
+    if (int rc = view_for(h, 1, false, &v)) return rc;
+    return pixels_launch(h, v, nullptr, mask_dev, v.n, height, width, channels, copies, out_dev, env_stride, copy_stride);
+}
+
+int mxv_pixels_host(mxv_handle *h, const int32_t *indices_host, int64_t count, int32_t height, int32_t width, int32_t channels,
+                    uint8_t *out_host) {
+    if (int rc = check_args(h, count, indices_host != nullptr, out_host)) return rc;
+    if (int rc = pixel_args(h, height, width, channels, 1)) return rc;
+    RenderView v;
+    if (int rc = view_for(h, count, indices_host != nullptr, &v)) return rc;
+    const int64_t frame = (int64_t)height * width * channels;
+    const size_t bytes = (size_t)frame * (size_t)count;
+    DeviceBuffer out, idx;
+    if (hipMalloc(&out.p, bytes) != hipSuccess) return render_fail(h, MXV_ERR_HIP, "pixels: hipMalloc of the output buffer failed");
+    if (indices_host) {
+        if (hipMalloc(&idx.p, (size_t)count * sizeof(int32_t)) != hipSuccess ||
+            hipMemcpyAsync(idx.p, indices_host, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, v.stream) != hipSuccess)
+            return render_fail(h, MXV_ERR_HIP, "pixels: staging the index list failed");
+    }
+    if (int rc = pixels_launch(h, v, (const int32_t *)idx.p, nullptr, count, height, width, channels, 1, (uint8_t *)out.p, frame, 0))
+        return rc;
+    if (hipMemcpyAsync(out_host, out.p, bytes, hipMemcpyDeviceToHost, v.stream) != hipSuccess || hipStreamSynchronize(v.stream) != hipSuccess)
+        return render_fail(h, MXV_ERR_HIP, "pixels: copying the frames back failed");
+    return mxv_sync(h);  // reports an index outside [0, N)
 }
 
 }  // extern "C"

@@ -22,6 +22,8 @@ struct RenderView {
 
 // Makes the handle's device current and its state fp64-resident (mxv_adopt_obs), then fills *v.  MXV_ERR_* on failure (message set).
 int render_view(mxv_handle *h, RenderView *v);
+// The handle's env kind (no device work).
+int32_t render_env_id(const mxv_handle *h);
 // Records `message` as the handle's last error and returns `code`.
 int render_fail(mxv_handle *h, int code, const char *message);
 

@@ -136,6 +136,26 @@ class DeviceRollout:
         _render.render_device(self.handle, out, indices, k)
         return out
 
+    def pixels(self, indices: Optional[torch.Tensor] = None, *, height: int = 84, width: int = 84, grayscale: bool = True,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Pixel observations of the current states, reduced on the device from the frames render() draws without writing those
+        anywhere: torch.uint8 [k, height, width] (gray, the reference's GrayScaleObservation weights) or
+        [k, height, width, 3], area-resized (ResizeObservation's place; the rule is adaptive_avg_pool2d's windows with integer
+        rounding).  `indices` / `out` / ordering / index errors as in render()."""
+        from . import _render
+
+        shape = _render.pixel_shape(self.spec.kind, height, width, grayscale)
+        if indices is not None:
+            assert indices.is_cuda and indices.dtype == torch.int32 and indices.is_contiguous() and indices.dim() == 1
+        k = self.num_envs if indices is None else indices.numel()
+        if out is None:
+            with torch.cuda.stream(self.stream):
+                out = torch.empty((k,) + shape, dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (k,) + shape
+        self._order_after_caller()
+        _render.pixels_device(self.handle, out, height, width, grayscale, indices, k)
+        return out
+
     def enable_graph_capture(self, on: bool = True):
         """Make this engine's calls recordable into a hipGraph of the CALLER's (torch.cuda.graph, hipStreamBeginCapture): the vector-step
         index moves into device memory and advances on the stream (mxv_set_device_clock), so that a replayed graph continues the

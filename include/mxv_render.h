@@ -54,6 +54,35 @@ int mxv_render_host(mxv_handle *h, const int32_t *indices_host, int64_t count, u
  * memory (see the record layout above).  Synchronises. */
 int mxv_render_scene_host(mxv_handle *h, const int32_t *indices_host, int64_t count, int32_t *records_host);
 
+/* -- pixel observations: the frame reduced to what a pixel learner reads (tests/pixels_host.py) ----------------------
+ * A pixel observation of size height x width (1 <= height <= H, 1 <= width <= W) with `channels` 1 (gray) or 3 (RGB) is a function
+ * of the frame above, computed without writing the frame anywhere:
+ *   gray (first):  Y = (4899 R + 9617 G + 1868 B + 8192) >> 14 per source pixel (OpenCV's documented fixed-point BT.601 weights);
+ *   area resize:   output pixel (i, j) is the rounded mean (sum + n / 2) / n, in integers, over the n source pixels of rows
+ *                  [floor(i H / height), ceil((i + 1) H / height)) and columns [floor(j W / width), ceil((j + 1) W / width))
+ *                  (torch.nn.functional.adaptive_avg_pool2d's windows; NOT OpenCV's INTER_AREA at non-integer ratios).
+ * Layout uint8 [height][width] (gray) or [height][width][3], row 0 at the top.  The pipeline it replaces: the reference's
+ * PixelObservationWrapper -> GrayScaleObservation -> ResizeObservation (pixel_observation.py:165-190, gray_scale_observation.py:50-64,
+ * resize_observation.py:48-70).  Attributes, indices, errors and stream order are those of mxv_render.  Argument errors (height /
+ * width out of range, channels not 1 or 3, copies < 1, NULL outputs, strides below one observation, a misaligned output or index
+ * pointer of mxv_pixels) return MXV_ERR_INVALID_ARG, and Pendulum MXV_ERR_UNSUPPORTED, before the device is touched. */
+
+/* Observations of `count` envs into out_dev (uint8 [count][height][width][channels], device, 16-byte aligned): observation k shows
+ * env indices_dev[k] (int32, device; repeats allowed), or env k when indices_dev is NULL (then count <= N). */
+int mxv_pixels(mxv_handle *h, const int32_t *indices_dev, int64_t count, int32_t height, int32_t width, int32_t channels,
+               uint8_t *out_dev);
+
+/* Observations of every env i whose mask_dev[i] is nonzero (uint8 [N], device; NULL = all envs) written `copies` times, to
+ * out_dev + i * env_stride + c * copy_stride (bytes; c < copies): copies = 1 pushes a frame into one slot of a frame stack
+ * (FrameStack, frame_stack.py:164-189), copies = num_stack fills the stack of a reset env.  16-byte stores wherever the
+ * destination is 16-byte aligned, narrower stores elsewhere.  Workgroups of masked-out envs return after reading the mask. */
+int mxv_pixels_strided(mxv_handle *h, const uint8_t *mask_dev, int32_t height, int32_t width, int32_t channels, int32_t copies,
+                       uint8_t *out_dev, int64_t env_stride, int64_t copy_stride);
+
+/* mxv_pixels into host memory with host indices (or NULL): synchronises, reports index errors itself. */
+int mxv_pixels_host(mxv_handle *h, const int32_t *indices_host, int64_t count, int32_t height, int32_t width, int32_t channels,
+                    uint8_t *out_host);
+
 #ifdef __cplusplus
 }
 #endif
