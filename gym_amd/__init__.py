@@ -16,6 +16,7 @@ _LAZY = {
     "HipEnv": ("gym_amd.single_env", "HipEnv"),
     "DeviceRollout": ("gym_amd.rollout", "DeviceRollout"),
     "PixelRollout": ("gym_amd.pixels", "PixelRollout"),
+    "pendulum_arrow_image": ("gym_amd.arrow", "pendulum_arrow_image"),
     "ShardedRollout": ("gym_amd.distributed", "ShardedRollout"),
     "MixedRollout": ("gym_amd.mixed", "MixedRollout"),
     "RecordEpisodeStatistics": ("gym_amd.wrappers", "RecordEpisodeStatistics"),

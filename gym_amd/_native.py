@@ -844,10 +844,15 @@ class Handle(_Engine):
     def snapshot(self) -> dict:
         """Everything a fresh handle needs to continue this one bit-identically (plain NumPy / ints: picklable): env state,
         TimeLimit counters, RNG seeds and counters, physics parameters, running episode returns."""
-        return dict(super().snapshot(), format=SNAPSHOT_FORMAT, env_id=self.env_id, max_episode_steps=self.max_episode_steps,
+        snap = dict(super().snapshot(), format=SNAPSHOT_FORMAT, env_id=self.env_id, max_episode_steps=self.max_episode_steps,
                     env_offset=self.env_offset, flags=self.flags, episodes=self.get_episodes(),
                     params=self.get_params_per_env() if self._per_env_params else self.get_params(),
                     per_env_params=self._per_env_params, beyond=self.get_beyond())
+        if getattr(self, "_arrow_image", None) is not None:   # Pendulum frames: the reference's last_u (gym_amd._render, NaN = None)
+            from . import _render
+
+            snap["last_u"] = _render.get_torques(self)
+        return snap
 
     def restore(self, snap: dict):
         # format 2 (round 2): reset draws are indexed by per-env reset ordinals (`episodes`).  Older snapshots carry no ordinals and
@@ -877,6 +882,17 @@ class Handle(_Engine):
         self.set_episodes(snap["episodes"])
         if snap.get("beyond") is not None:             # after set_state (which clears the marks: an injected state is a fresh one)
             self.set_beyond(snap["beyond"])
+        if snap.get("last_u") is not None:
+            if getattr(self, "_arrow_image", None) is None:
+                raise ValueError("the snapshot carries Pendulum's last_u (it was taken with an arrow image attached): attach one first "
+                                 "(arrow_image=)")
+            from . import _render
+
+            _render.set_torques(self, snap["last_u"])
+        elif getattr(self, "_arrow_image", None) is not None:   # a snapshot taken without an image: no env has a torque to draw
+            from . import _render
+
+            _render.set_torques(self, np.full(self.num_envs, np.nan, np.float32))
 
     def get_beyond(self) -> np.ndarray:
         """CartPole's steps_beyond_terminated marks (uint8 [N]; all zero for handles that keep none: mxv_get_beyond)."""

@@ -19,6 +19,7 @@
 #include "mxv_host.hpp"
 #include "mxv_kernels.hpp"
 #include "mxv_render.hpp"
+#include "../../include/mxv_render.h"
 
 using namespace mxv;
 
@@ -128,6 +129,12 @@ struct mxv_handle : mxv::HostCore {
     uint8_t *snap_term = nullptr, *snap_trunc = nullptr;
     hipEvent_t ev_wait = nullptr;   // mxv_wait_stream
     hipEvent_t ev_mixed = nullptr;  // orders this handle's stream against a mixed-batch launch issued on another handle's stream
+    // Pendulum frames (mxv_render_attach_image): the arrow's summed-area table and the reference's last_u, kept by every stepping and
+    // resetting call (track_*) once an image is attached
+    uint4 *blit_sat = nullptr;      // [blit_h + 1][blit_w + 1]
+    int32_t blit_h = 0, blit_w = 0;
+    float *last_u = nullptr;        // [N], NaN = None
+    float *blit_actions = nullptr;  // [N] the last step's sampled actions, drawn again from the action stream (track_source)
 
     size_t action_bytes() const {
         if (NA > 0) return (cfg.flags & MXV_FLAG_ACTION_I32) ? 4 : 8;
@@ -204,6 +211,39 @@ void fill_step_args(mxv_handle *h, StepArgs &a) {
     a.snap_reward = nullptr;
     a.snap_terminated = a.snap_truncated = nullptr;
     a.P = h->P;
+}
+
+// -- last_u of a Pendulum handle with an arrow image (mxv_render.h): one small launch behind each stepping / resetting call -----------
+// Where the actions of the LAST of the next K steps will be, queued BEFORE the step launch: the caller's actions (`actions` + row * N), or
+// for sampled steps the same draw again from the counter-based action stream (mxv_sample_actions' kernel at step index t + K - 1) into
+// blit_actions.  *src = nullptr when the handle tracks nothing.
+int track_source(mxv_handle *h, const void *actions, int64_t row, int32_t K, const float **src) {
+    *src = nullptr;
+    if (!h->last_u) return MXV_OK;
+    if (actions) {
+        *src = (const float *)actions + row * h->cfg.num_envs;
+        return MXV_OK;
+    }
+    SampleArgs a{};
+    a.actions_out = h->blit_actions;
+    a.t_dev = h->dev_clock ? h->t_dev : nullptr;
+    a.t = (h->dev_clock ? 0 : h->t) + (uint64_t)(K - 1);
+    a.n = h->cfg.num_envs;
+    a.env0 = (uint64_t)h->cfg.env_offset;
+    a.action_seed = h->action_seed;
+    a.flags = h->cfg.flags;
+    a.params_pe = h->params_pe;
+    a.P = h->P;
+    MXV_HIP(h, launch_sample(h->cfg.env_id, h->param_mode(), a, h->stream));
+    *src = h->blit_actions;
+    return MXV_OK;
+}
+
+// After the step launch: last_u = the clip of those actions, None where the call autoreset the env.
+int track_step(mxv_handle *h, const float *src) {
+    if (!h->last_u || !src) return MXV_OK;
+    MXV_HIP(h, launch_track_step(h->last_u, src, h->elapsed, h->elapsed16 ? 1 : 0, h->params_pe, h->P.p[1], h->cfg.num_envs, h->stream));
+    return MXV_OK;
 }
 
 // launches that never form the fused batch moments: with a buffer attached they fail instead of leaving it stale
@@ -296,6 +336,8 @@ int do_step(mxv_handle *h, const void *actions, void *actions_out, float *obs, v
         a.clock_ticket = h->clock_ticket;
     }
     if (int rc = check_step_buffers(h, a)) return rc;
+    const float *track = nullptr;
+    if (int rc = track_source(h, actions, 0, 1, &track)) return rc;
     if (hilo_step) {
         a.hi_in = h->adopted_obs;
         a.lo = h->lo;
@@ -304,6 +346,7 @@ int do_step(mxv_handle *h, const void *actions, void *actions_out, float *obs, v
         MXV_HIP(h, launch_step(h->cfg.env_id, h->param_mode(), a, h->stream, &h->last_launch));
     }
     h->state_injected = false;
+    if (int rc = track_step(h, track)) return rc;
     if (self_clock) {
         h->t += 1;
         return MXV_OK;
@@ -347,6 +390,7 @@ int do_reset(mxv_handle *h, const uint8_t *mask_dev, const double *bounds, float
     a.b1 = b[1];
     if (int rc = check_aligned(h, a.obs, h->O == 4 ? 16 : ((h->O % 2 == 0) ? 8 : 4), "obs")) return rc;
     MXV_HIP(h, launch_reset(h->cfg.env_id, a, h->stream));
+    if (h->last_u) MXV_HIP(h, launch_track_reset(h->last_u, mask_dev, h->cfg.num_envs, h->stream));
     h->was_reset = true;
     if (mask_dev == nullptr) h->state_out_of_range = false;  // every env re-drawn
     // CartPole's range-reduction-free sin/cos (rollout fast path, SAFE = false) assumes |theta| <= pi/4 on entry; reset bounds
@@ -603,7 +647,8 @@ int mxv_destroy(mxv_handle *h) {
     free_graphs(h);
     if (h->hm_block) (void)hipHostFree(h->hm_block);
     if (h->fin_host) (void)hipHostFree(h->fin_host);
-    free_core(h, {h->fin_dev, h->lo, h->state, h->elapsed, h->episodes, h->clock_ticket, h->params_pe, h->dv_block, h->beyond});
+    free_core(h, {h->fin_dev, h->lo, h->state, h->elapsed, h->episodes, h->clock_ticket, h->params_pe, h->dv_block, h->beyond,
+                  h->blit_sat, h->last_u, h->blit_actions});
     delete h;
     return MXV_OK;
 }
@@ -707,8 +752,11 @@ int fused_launch(mxv_handle *h, int32_t K, int32_t per_step, const void *actions
         a.snap_truncated = h->snap_trunc;
     }
     if (int rc = check_step_buffers(h, a)) return rc;
+    const float *track = nullptr;
+    if (int rc = track_source(h, actions_tape, K - 1, K, &track)) return rc;
     MXV_HIP(h, launch_step(h->cfg.env_id, h->param_mode(), a, h->stream, &h->last_launch));
     h->state_injected = false;
+    if (int rc = track_step(h, track)) return rc;
     if (int rc = clock_add(h, K)) return rc;
     if (h->snap_obs && !in_kernel) return copy_final_snapshot(h, K, per_step, obs, reward, term, trunc);
     return MXV_OK;
@@ -754,6 +802,8 @@ int mxv_rollout(mxv_handle *h, int32_t K, int32_t per_step, int32_t mode, void *
         a.ep_length_out = (int32_t *)slice(a.ep_length_out, sizeof(int32_t), k);
         return launch_step(h->cfg.env_id, h->param_mode(), a, h->stream, &h->last_launch);
     };
+    const float *track = nullptr;
+    if (int rc = track_source(h, nullptr, 0, K, &track)) return rc;
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(h->stream, &capturing);   // inside a caller's capture: plain launches (they are being recorded already)
     if (mode == MXV_ROLLOUT_EAGER || capturing != hipStreamCaptureStatusNone) {
@@ -786,6 +836,7 @@ int mxv_rollout(mxv_handle *h, int32_t K, int32_t per_step, int32_t mode, void *
         MXV_HIP(h, hipGraphLaunch(it->second, h->stream));
     }
     h->state_injected = false;
+    if (int rc = track_step(h, track)) return rc;
     if (int rc = clock_add(h, K)) return rc;
     if (h->snap_obs) return copy_final_snapshot(h, K, per_step, obs_dev, reward_dev, terminated_dev, truncated_dev);
     return MXV_OK;
@@ -1709,11 +1760,89 @@ int render_view(mxv_handle *h, RenderView *v) {
     v->params_pe = h->params_pe;
     std::memcpy(v->P, h->P.p, sizeof v->P);
     v->err = h->err;
+    v->last_u = h->last_u;
+    v->sat = h->blit_sat;
+    v->img_h = h->blit_h;
+    v->img_w = h->blit_w;
     return MXV_OK;
 }
 
 int32_t render_env_id(const mxv_handle *h) { return h->cfg.env_id; }
 
+bool render_ready(const mxv_handle *h) { return h->cfg.env_id != MXV_PENDULUM || h->blit_sat != nullptr; }
+
 int render_fail(mxv_handle *h, int code, const char *message) { return fail(h, code, "%s", message); }
 
 }  // namespace mxv
+
+// -- Pendulum's arrow image and last_u (include/mxv_render.h) ---------------------------------------------------------------------------
+extern "C" {
+
+int mxv_render_frame_dims(mxv_handle *h, int32_t *height, int32_t *width) {
+    MXV_CHECK(h);
+    if (!height || !width) return fail(h, MXV_ERR_INVALID_ARG, "render: NULL outputs");
+    if (h->cfg.env_id == MXV_PENDULUM) {
+        if (!h->blit_sat)
+            return fail(h, MXV_ERR_UNSUPPORTED, "render: Pendulum-v1 draws an image asset (pendulum.py:228-244) that the engine does not carry: "
+                                                "attach one first (mxv_render_attach_image)");
+        *height = *width = 500;
+        return MXV_OK;
+    }
+    const int rc = mxv_render_dims(h->cfg.env_id, height, width);
+    return rc == MXV_OK ? rc : fail(h, rc, "render: the toy_text engines have no frames");
+}
+
+int mxv_render_attach_image(mxv_handle *h, const uint8_t *rgba_host, int32_t height, int32_t width) {
+    MXV_CHECK(h);
+    if (h->cfg.env_id != MXV_PENDULUM) return fail(h, MXV_ERR_UNSUPPORTED, "render: only Pendulum-v1 frames blit an image");
+    if (!rgba_host) return fail(h, MXV_ERR_INVALID_ARG, "render: image pointer is NULL");
+    if (height < 1 || height > 1024 || width < 1 || width > 1024)
+        return fail(h, MXV_ERR_INVALID_ARG, "render: the image must be 1 .. 1024 pixels high and wide (got %d x %d)", height, width);
+    if (int rc = use_device(h)) return rc;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone)
+        return fail(h, MXV_ERR_UNSUPPORTED, "render: an image cannot be attached while the handle's stream is being captured");
+    const size_t n = (size_t)h->cfg.num_envs, img = (size_t)height * width * 4, table = (size_t)(height + 1) * (width + 1) * sizeof(uint4);
+    MXV_HIP(h, hipStreamSynchronize(h->stream));   // frames already queued read the old table
+    if (h->blit_sat) MXV_HIP(h, hipFree(h->blit_sat));
+    h->blit_sat = nullptr;
+    if (!h->last_u) MXV_HIP(h, hipMalloc((void **)&h->last_u, n * sizeof(float)));
+    if (!h->blit_actions) MXV_HIP(h, hipMalloc((void **)&h->blit_actions, n * sizeof(float)));
+    uint4 *sat = nullptr;
+    MXV_HIP(h, hipMalloc((void **)&sat, table));
+    uint8_t *staged = nullptr;
+    hipError_t e = hipMalloc((void **)&staged, img);
+    if (e == hipSuccess) e = hipMemcpyAsync(staged, rgba_host, img, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = launch_blit_table(staged, sat, height, width, h->stream);
+    if (e == hipSuccess) e = launch_track_reset(h->last_u, nullptr, h->cfg.num_envs, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (staged) (void)hipFree(staged);
+    if (e != hipSuccess) {
+        (void)hipFree(sat);
+        return fail(h, MXV_ERR_HIP, "render: attaching the image failed: %s", hipGetErrorString(e));
+    }
+    h->blit_sat = sat;
+    h->blit_h = height;
+    h->blit_w = width;
+    return MXV_OK;
+}
+
+static int torques_io(mxv_handle *h, void *dst, const void *src, hipMemcpyKind kind) {
+    MXV_CHECK(h);
+    if (!h->last_u) return fail(h, MXV_ERR_UNSUPPORTED, "render: no image attached (mxv_render_attach_image): the handle tracks no last_u");
+    if (!dst || !src) return fail(h, MXV_ERR_INVALID_ARG, "render: NULL last_u buffer");
+    if (int rc = use_device(h)) return rc;
+    MXV_HIP(h, hipMemcpyAsync(dst, src, (size_t)h->cfg.num_envs * sizeof(float), kind, h->stream));
+    MXV_HIP(h, hipStreamSynchronize(h->stream));
+    return MXV_OK;
+}
+
+int mxv_render_get_torques_host(mxv_handle *h, float *last_u_host) {
+    return torques_io(h, last_u_host, h ? h->last_u : nullptr, hipMemcpyDeviceToHost);
+}
+
+int mxv_render_set_torques_host(mxv_handle *h, const float *last_u_host) {
+    return torques_io(h, h ? h->last_u : nullptr, last_u_host, hipMemcpyHostToDevice);
+}
+
+}  // extern "C"

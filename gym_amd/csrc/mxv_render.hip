@@ -22,10 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#define MXV_XFN __device__ inline
-#define MXV_XCONST __device__ const
-#define MXV_XCOLD __device__ __noinline__ inline
-#include "mxv_exact.hpp"
+#include "mxv_device.hpp"   // mxv_exact.hpp (correctly rounded sin / cos) and clamp_range, the clip of the Pendulum step
 #include "mxv_render.hpp"
 #include "../../include/mxv_render.h"
 
@@ -41,9 +38,10 @@ constexpr double kLimitPx = 1048576.0;  // 2^20: coordinates beyond it (or non-f
 constexpr double kTwoPi = 2 * M_PI, kHalfPi = M_PI / 2, kVectorEpsilon = 1e-6;
 constexpr int64_t kMaxCount = (int64_t)1 << 24;
 
-__host__ __device__ inline int frame_h(int kind) { return kind == MXV_ACROBOT ? 500 : 400; }
-__host__ __device__ inline int frame_w(int kind) { return kind == MXV_ACROBOT ? 500 : 600; }
-__host__ __device__ inline int kind_records(int kind) { return kind == MXV_CARTPOLE ? 7 : kind == MXV_ACROBOT ? 9 : 108; }
+__host__ __device__ inline bool square_frame(int kind) { return kind == MXV_ACROBOT || kind == MXV_PENDULUM; }
+__host__ __device__ inline int frame_h(int kind) { return square_frame(kind) ? 500 : 400; }
+__host__ __device__ inline int frame_w(int kind) { return square_frame(kind) ? 500 : 600; }
+__host__ __device__ inline int kind_records(int kind) { return kind == MXV_CARTPOLE ? 7 : square_frame(kind) ? 9 : 108; }
 
 // (sin x, cos x): correctly rounded where mxv_exact.hpp covers the argument, the device libm beyond, NaN for non-finite x
 __device__ inline void sincos_rn(double x, double *s, double *c) {
@@ -126,8 +124,25 @@ __device__ inline double mc_height(double v) {
     return s * 0.45 + 0.55;
 }
 
-// The frame's records into rec[kMaxRec][kRec] (LDS).  Called by every thread of the block; ends with a barrier.
-__device__ void build_scene(int kind, const double *s, const double *P, int32_t (*rec)[kRec], double *tx, double *ty) {
+// Pendulum's arrow (pendulum.py:235-244): smoothscale to (scale * |last_u| / 2,) * 2 — float32 arithmetic (NumPy 2 keeps the Python
+// float weak), int() of the size as for every gfxdraw argument — flipped horizontally when last_u > 0 and always vertically, blitted at
+// (offset - w // 2, offset - h // 2) (Rect.centerx / centery).  No record for None (NaN) or a size beyond the coordinate limit.
+__device__ inline void put_blit(int32_t *r, float u, double scale, int offset) {
+    for (int i = 0; i < kRec; ++i) r[i] = 0;
+    const float size = (float)scale * fabsf(u) / 2.0f;
+    if (!(size <= (float)kLimitPx)) return;
+    const int32_t wh = (int32_t)size;
+    r[0] = MXV_RENDER_BLIT;
+    r[4] = offset - wh / 2;
+    r[5] = offset - wh / 2;
+    r[6] = wh;
+    r[7] = wh;
+    r[8] = u > 0.0f ? 1 : 0;
+    r[9] = 1;
+}
+
+// The frame's records into rec[kMaxRec][kRec] (LDS).  Called by every thread of the block; ends with a barrier.  `u`: Pendulum's last_u.
+__device__ void build_scene(int kind, const double *s, const double *P, float u, int32_t (*rec)[kRec], double *tx, double *ty) {
     const int t = threadIdx.x;
     const int nrec = kind_records(kind);
     for (int i = nrec + t; i < kMaxRec; i += blockDim.x)
@@ -189,6 +204,33 @@ __device__ void build_scene(int kind, const double *s, const double *P, int32_t 
                 put_circle(rec[3 + 4 * k], MXV_RENDER_AACIRCLE, 0xCCCC00u, x, y, 0.1 * scale);
                 put_circle(rec[4 + 4 * k], MXV_RENDER_FILLED_CIRCLE, 0xCCCC00u, x, y, 0.1 * scale);
             }
+        }
+    } else if (kind == MXV_PENDULUM) {  // pendulum.py:197-249
+        if (t == 0) {
+            const double bound = 2.2;
+            const double scale = 500 / (bound * 2);
+            const int offset = 500 / 2;
+            const double rod_length = 1 * scale, rod_width = 0.2 * scale;
+            const double l = 0, r = rod_length, tp = rod_width / 2, b = -rod_width / 2;
+            const double src[4][2] = {{l, b}, {l, tp}, {r, tp}, {r, b}};
+            const double angle = s[0] + M_PI / 2;
+            double q[4][2];
+            for (int j = 0; j < 4; ++j) {
+                double cx, cy;
+                rotate_rad(src[j][0], src[j][1], angle, &cx, &cy);
+                q[j][0] = cx + offset;
+                q[j][1] = cy + offset;
+            }
+            put_quad(rec[0], 0xCC4D4Du, q);
+            put_circle(rec[2], MXV_RENDER_AACIRCLE, 0xCC4D4Du, offset, offset, rod_width / 2);
+            put_circle(rec[3], MXV_RENDER_FILLED_CIRCLE, 0xCC4D4Du, offset, offset, rod_width / 2);
+            double ex, ey;   // rod_end: int() of the rotated (rod_length, 0) plus the offset, then gfxdraw's int() again (a no-op)
+            rotate_rad(rod_length, 0.0, angle, &ex, &ey);
+            put_circle(rec[4], MXV_RENDER_AACIRCLE, 0xCC4D4Du, ex + offset, ey + offset, rod_width / 2);
+            put_circle(rec[5], MXV_RENDER_FILLED_CIRCLE, 0xCC4D4Du, ex + offset, ey + offset, rod_width / 2);
+            put_blit(rec[6], u, scale, offset);
+            put_circle(rec[7], MXV_RENDER_AACIRCLE, 0x000000u, offset, offset, 0.05 * scale);
+            put_circle(rec[8], MXV_RENDER_FILLED_CIRCLE, 0x000000u, offset, offset, 0.05 * scale);
         }
     } else {  // MountainCar-v0 (0 min_position 1 max_position 3 goal_position) / MountainCarContinuous-v0 (2, 3, 5)
         const bool cont = kind == MXV_MOUNTAINCAR_CONT;
@@ -358,6 +400,11 @@ __device__ inline void record_bbox(const int32_t *r, int H, int W, int32_t *bb) 
         bb[0] = 1, bb[1] = 0, bb[2] = 1, bb[3] = 0;
         return;
     }
+    if (op == MXV_RENDER_BLIT) {   // whole pixels [x, x + w) x [y, y + h); w = 0: empty
+        bb[0] = max(r[4], 0), bb[1] = (int32_t)min((int64_t)r[4] + r[6] - 1, (int64_t)W - 1);
+        bb[2] = max(r[5], 0), bb[3] = (int32_t)min((int64_t)r[5] + r[7] - 1, (int64_t)H - 1);
+        return;
+    }
     int64_t x0 = r[4], x1 = r[4], y0 = r[5], y1 = r[5];
 #pragma unroll
     for (int k = 1; k < 4; ++k) {
@@ -380,9 +427,12 @@ struct RenderArgs {
     uint8_t *frames;       // render_kernel: [count][H][W][3]
     int32_t *records;      // scene_kernel: [count][kMaxRec][kRec]
     int32_t *err;
+    const float *last_u;   // Pendulum: [N] or nullptr (no arrow)
+    const uint4 *sat;      // Pendulum: the arrow's summed-area table [img_h + 1][img_w + 1]
     int64_t n;
     int32_t kind;
     int32_t S;
+    int32_t img_h, img_w;
     double P[MXV_MAX_PARAMS];
 };
 
@@ -392,11 +442,12 @@ struct SceneLds {
 };
 
 // the env a frame shows, its state and its attributes; false (uniform over the block) for an index outside [0, N)
-__device__ inline bool load_env(const RenderArgs &a, int64_t frame, double *s, double *P) {
+__device__ inline bool load_env(const RenderArgs &a, int64_t frame, double *s, double *P, float *u) {
     const int64_t env = a.idx ? (int64_t)a.idx[frame] : frame;
     if (env < 0 || env >= a.n) return false;
     for (int k = 0; k < 4; ++k) s[k] = k < a.S ? a.state[(size_t)k * a.n + env] : 0.0;
     for (int k = 0; k < MXV_MAX_PARAMS; ++k) P[k] = a.params_pe ? a.params_pe[(size_t)k * a.n + env] : a.P[k];
+    *u = a.last_u ? a.last_u[env] : NAN;
     return true;
 }
 
@@ -405,12 +456,13 @@ __global__ __launch_bounds__(kThreads) void scene_kernel(RenderArgs a) {
     const int64_t frame = blockIdx.x;
     int32_t *out = a.records + (size_t)frame * kMaxRec * kRec;
     double s[4], P[MXV_MAX_PARAMS];
-    if (!load_env(a, frame, s, P)) {
+    float u;
+    if (!load_env(a, frame, s, P, &u)) {
         if (threadIdx.x == 0) atomicOr(a.err, kRenderIndexErrorBit);
         for (int i = threadIdx.x; i < kMaxRec * kRec; i += blockDim.x) out[i] = 0;
         return;
     }
-    build_scene(a.kind, s, P, L.rec, L.tx, L.ty);
+    build_scene(a.kind, s, P, u, L.rec, L.tx, L.ty);
     for (int i = threadIdx.x; i < kMaxRec * kRec; i += blockDim.x) out[i] = L.rec[i / kRec][i % kRec];
 }
 
@@ -471,14 +523,45 @@ __device__ inline void run_candidates(const CullLds &C, int nl, int rx0, int rx1
     *cand1 = c1;
 }
 
+// The MXV_RENDER_BLIT record r over colour 0xRRGGBB at surface pixel (x, y) inside its box (include/mxv_render.h): the scaled image's
+// pixel is the rounded window mean of the straight RGBA source, four corner loads of the summed-area table; then the alpha blend.
+// Not inlined: the other kinds never reach it, and it adds nothing to shade()'s registers (its arguments travel by value: a reference to
+// the kernel's argument block would put a copy of that block in scratch).
+__device__ __noinline__ uint32_t blit_pixel(const int32_t *r, const uint4 *sat, int32_t img_h, int32_t img_w, int x, int y, uint32_t rgb) {
+    const int64_t w = r[6], h = r[7], Hs = img_h, Ws = img_w;
+    int64_t row = y - r[5], col = x - r[4];
+    if (r[9]) row = h - 1 - row;
+    if (r[8]) col = w - 1 - col;
+    const int64_t r0 = row * Hs / h, r1 = ((row + 1) * Hs + h - 1) / h;
+    const int64_t c0 = col * Ws / w, c1 = ((col + 1) * Ws + w - 1) / w;
+    const uint4 p = sat[r1 * (Ws + 1) + c1], q = sat[r0 * (Ws + 1) + c1], s = sat[r1 * (Ws + 1) + c0], t = sat[r0 * (Ws + 1) + c0];
+    const uint32_t n = (uint32_t)((r1 - r0) * (c1 - c0));
+    const uint32_t mr = (p.x - q.x - s.x + t.x + n / 2) / n, mg = (p.y - q.y - s.y + t.y + n / 2) / n;
+    const uint32_t mb = (p.z - q.z - s.z + t.z + n / 2) / n, ma = (p.w - q.w - s.w + t.w + n / 2) / n;
+    const uint32_t o = 255 - ma;
+    const uint32_t cr = (mr * ma + ((rgb >> 16) & 255) * o + 127) / 255;
+    const uint32_t cg = (mg * ma + ((rgb >> 8) & 255) * o + 127) / 255;
+    const uint32_t cb = (mb * ma + (rgb & 255) * o + 127) / 255;
+    return cr << 16 | cg << 8 | cb;
+}
+
 // The colour 0xRRGGBB of surface pixel (x, y): white, then every candidate record that covers samples of it blended in draw order.
-__device__ inline uint32_t shade(const SceneLds &L, const CullLds &C, uint64_t cand0, uint64_t cand1, int x, int y) {
+// BLIT: the scene may hold Pendulum's arrow (a.sat set).  The callers pick the instance by a uniform branch on a.sat, so the other kinds
+// run the loop without the blit test.
+template <bool BLIT>
+__device__ inline uint32_t shade(const RenderArgs &a, const SceneLds &L, const CullLds &C, uint64_t cand0, uint64_t cand1, int x, int y) {
     uint32_t cr = 255, cg = 255, cb = 255;
     for (int h = 0; h < 2; ++h)
     for (uint64_t mm = h ? cand1 : cand0; mm; mm &= mm - 1) {
         const int k = C.list[h * 64 + __ffsll((unsigned long long)mm) - 1];
         if (x < C.bbox[k][0] || x > C.bbox[k][1] || y < C.bbox[k][2] || y > C.bbox[k][3]) continue;
         const int32_t *r = L.rec[k];
+        // Pendulum's arrow (its box is the image's rectangle: every pixel of it is drawn)
+        if (BLIT && r[0] == MXV_RENDER_BLIT) {
+            const uint32_t c = blit_pixel(r, a.sat, a.img_h, a.img_w, x, y, cr << 16 | cg << 8 | cb);
+            cr = c >> 16, cg = (c >> 8) & 255, cb = c & 255;
+            continue;
+        }
         const int c = coverage(r, x, y);
         if (c == 0) continue;
         const uint32_t rgb = (uint32_t)r[1], o = 16 - c;
@@ -517,12 +600,13 @@ __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
     uint4 *o4 = (uint4 *)(a.frames + frame * kFrameBytes + (int64_t)row0 * W * 3);
     const int t = threadIdx.x;
     double s[4], P[MXV_MAX_PARAMS];
-    if (!load_env(a, frame, s, P)) {
+    float u;
+    if (!load_env(a, frame, s, P, &u)) {
         if (t == 0 && band == 0) atomicOr(a.err, kRenderIndexErrorBit);
         for (int run = t; run < runs; run += kThreads) store_run(o4 + 3 * run, 0u);
         return;
     }
-    build_scene(a.kind, s, P, L.rec, L.tx, L.ty);
+    build_scene(a.kind, s, P, u, L.rec, L.tx, L.ty);
     // records that reach this band's rows, in draw order (surface y of output row R is H - 1 - R)
     if (t < kMaxRec) record_bbox(L.rec[t], H, W, C.bbox[t]);
     const int nl = cull_records(C, H - row0 - rows, H - 1 - row0);
@@ -545,7 +629,7 @@ __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
         for (int j = 0; j < 16; ++j) {
             int x = colA + j, y = yA;
             if (x >= W) x -= W, y -= 1;
-            const uint32_t c = shade(L, C, cand0, cand1, x, y);
+            const uint32_t c = a.sat ? shade<true>(a, L, C, cand0, cand1, x, y) : shade<false>(a, L, C, cand0, cand1, x, y);
             mine[3 * j] = (uint8_t)(c >> 16);
             mine[3 * j + 1] = (uint8_t)(c >> 8);
             mine[3 * j + 2] = (uint8_t)c;
@@ -627,12 +711,13 @@ __global__ __launch_bounds__(kThreads) void pixels_kernel(PixelArgs a) {
     const int nb = (i1 - i0) * rowb;                               // the band's output bytes (<= kMaxBandBytes, checked by the launch)
     uint8_t *dst0 = a.out + frame * a.env_stride + (int64_t)i0 * rowb;
     double s[4], P[MXV_MAX_PARAMS];
-    if (!load_env(a.r, frame, s, P)) {
+    float u;
+    if (!load_env(a.r, frame, s, P, &u)) {
         if (t == 0 && band == 0) atomicOr(a.r.err, kRenderIndexErrorBit);
         store_band(a, dst0, nb, nullptr, 0);
         return;
     }
-    build_scene(a.r.kind, s, P, L.rec, L.tx, L.ty);
+    build_scene(a.r.kind, s, P, u, L.rec, L.tx, L.ty);
     if (t < kMaxRec) record_bbox(L.rec[t], H, W, Cl.bbox[t]);
     const int r0 = (int)((int64_t)i0 * H / h), r1 = (int)(((int64_t)i1 * H + h - 1) / h);   // the band's source rows [r0, r1)
     const int chunks = (r1 - r0 + kRows - 1) / kRows;
@@ -661,7 +746,9 @@ __global__ __launch_bounds__(kThreads) void pixels_kernel(PixelArgs a) {
             for (int j = 0; j < n; ++j) {
                 int x = colA + j, y = yA;
                 if (x >= W) x -= W, y -= 1;
-                tile_put<C>(tile, p0 + j, (cand0 | cand1) ? shade(L, Cl, cand0, cand1, x, y) : 0xFFFFFFu);
+                const uint32_t rgb = !(cand0 | cand1) ? 0xFFFFFFu
+                                   : a.r.sat ? shade<true>(a.r, L, Cl, cand0, cand1, x, y) : shade<false>(a.r, L, Cl, cand0, cand1, x, y);
+                tile_put<C>(tile, p0 + j, rgb);
             }
         }
         __syncthreads();
@@ -704,6 +791,10 @@ RenderArgs render_args(const RenderView &v, const int32_t *idx_dev) {
     a.n = v.n;
     a.kind = v.env_id;
     a.S = v.env_id == MXV_ACROBOT || v.env_id == MXV_CARTPOLE ? 4 : 2;
+    a.last_u = v.last_u;
+    a.sat = v.sat;
+    a.img_h = v.img_h;
+    a.img_w = v.img_w;
     std::memcpy(a.P, v.P, sizeof a.P);
     return a;
 }
@@ -714,7 +805,7 @@ int launch(const RenderView &v, const int32_t *idx_dev, int64_t count, uint8_t *
     a.records = records;
     if (records) {
         hipLaunchKernelGGL(scene_kernel, dim3((unsigned)count), dim3(kThreads), 0, v.stream, a);
-    } else if (v.env_id == MXV_ACROBOT) {
+    } else if (square_frame(v.env_id)) {   // Acrobot, Pendulum
         hipLaunchKernelGGL((render_kernel<500, 500>), dim3((unsigned)(count * ((500 + kBandRows - 1) / kBandRows))), dim3(kThreads), 0,
                            v.stream, a);
     } else {
@@ -752,7 +843,7 @@ int launch_pixels(const RenderView &v, const int32_t *idx_dev, const uint8_t *ma
     a.band_rows = pixel_band_rows(H, frame_w(v.env_id), height, width, channels);
     a.bands = (height + a.band_rows - 1) / a.band_rows;
     const dim3 grid((unsigned)(frames * a.bands));
-    if (v.env_id == MXV_ACROBOT)
+    if (square_frame(v.env_id))
         launch_pixels_kind<500, 500>(a, channels, grid, v.stream);
     else
         launch_pixels_kind<400, 600>(a, channels, grid, v.stream);
@@ -772,10 +863,10 @@ int check_args(mxv_handle *h, int64_t count, bool have_idx, const void *out) {
 
 // the handle's view after the checks that need its size / kind (count > N without indices, unsupported kinds)
 int view_for(mxv_handle *h, int64_t count, bool have_idx, RenderView *v) {
-    if (int rc = render_view(h, v)) return rc;
-    if (!renderable(v->env_id))
+    if (!render_ready(h))
         return render_fail(h, MXV_ERR_UNSUPPORTED, "render: Pendulum-v1 draws an image asset (pendulum.py:228-244) that the engine does not "
-                                                   "carry: no rgb_array frames for it");
+                                                   "carry: no rgb_array frames for it until the caller attaches one (mxv_render_attach_image)");
+    if (int rc = render_view(h, v)) return rc;
     if (!have_idx && count > v->n) return render_fail(h, MXV_ERR_INVALID_ARG, "render: count > num_envs without an index list");
     return MXV_OK;
 }
@@ -787,7 +878,74 @@ struct DeviceBuffer {
     }
 };
 
+// -- Pendulum's arrow: the image's summed-area table and the per-env last_u ----------------------------------------------------------
+constexpr int kTableThreads = 1024;
+
+// sat[i][j] = per-channel sums of rgba over rows < i, columns < j (uint32: 1024 x 1024 x 255 < 2^32).  One workgroup: row prefixes, then
+// column prefixes, one thread per row / column.
+__global__ __launch_bounds__(kTableThreads) void blit_table_kernel(const uint8_t *rgba, uint4 *sat, int32_t h, int32_t w) {
+    const int64_t ld = (int64_t)w + 1;
+    for (int j = threadIdx.x; j <= w; j += blockDim.x) sat[j] = make_uint4(0, 0, 0, 0);
+    for (int i = threadIdx.x; i < h; i += blockDim.x) {
+        uint4 run = make_uint4(0, 0, 0, 0);
+        sat[(i + 1) * ld] = run;
+        for (int j = 0; j < w; ++j) {
+            const uint8_t *p = rgba + ((int64_t)i * w + j) * 4;
+            run.x += p[0], run.y += p[1], run.z += p[2], run.w += p[3];
+            sat[(i + 1) * ld + j + 1] = run;
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < w; j += blockDim.x) {
+        uint4 run = make_uint4(0, 0, 0, 0);
+        for (int i = 1; i <= h; ++i) {
+            const uint4 v = sat[i * ld + j + 1];
+            run.x += v.x, run.y += v.y, run.z += v.z, run.w += v.w;
+            sat[i * ld + j + 1] = run;
+        }
+    }
+}
+
+constexpr int kTrackThreads = 256;
+
+__global__ __launch_bounds__(kTrackThreads) void track_reset_kernel(float *last_u, const uint8_t *mask, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kTrackThreads + threadIdx.x;
+    if (i < n && (!mask || mask[i])) last_u[i] = NAN;
+}
+
+// The clip of Env<MXV_PENDULUM>::step (the same clamp_range of mxv_device.hpp: IEEE maximum / minimum, NaN passes through, -0 < +0), then
+// None where the step's autoreset ran (elapsed == 0 after a step happens only there).
+__global__ __launch_bounds__(kTrackThreads) void track_step_kernel(float *last_u, const float *actions, const void *elapsed, int32_t el16,
+                                                                  const double *params_pe, double max_torque, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kTrackThreads + threadIdx.x;
+    if (i >= n) return;
+    const double mt = params_pe ? params_pe[n + i] : max_torque;
+    const float lo = (float)(-mt), hi = (float)mt;
+    const float u = clamp_range(actions[i], lo, hi);
+    const int32_t el = el16 ? (int32_t) static_cast<const uint16_t *>(elapsed)[i] : static_cast<const int32_t *>(elapsed)[i];
+    last_u[i] = el == 0 ? NAN : u;
+}
+
 }  // namespace render
+
+hipError_t launch_blit_table(const uint8_t *rgba, uint4 *sat, int32_t h, int32_t w, hipStream_t stream) {
+    hipLaunchKernelGGL(render::blit_table_kernel, dim3(1), dim3(render::kTableThreads), 0, stream, rgba, sat, h, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_reset(float *last_u, const uint8_t *mask, int64_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(render::track_reset_kernel, dim3((unsigned)((n + render::kTrackThreads - 1) / render::kTrackThreads)),
+                       dim3(render::kTrackThreads), 0, stream, last_u, mask, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_step(float *last_u, const float *actions, const void *elapsed, int32_t elapsed16, const double *params_pe,
+                             double max_torque, int64_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(render::track_step_kernel, dim3((unsigned)((n + render::kTrackThreads - 1) / render::kTrackThreads)),
+                       dim3(render::kTrackThreads), 0, stream, last_u, actions, elapsed, elapsed16, params_pe, max_torque, n);
+    return hipGetLastError();
+}
+
 }  // namespace mxv
 
 using namespace mxv;
@@ -846,9 +1004,9 @@ int mxv_render_scene_host(mxv_handle *h, const int32_t *indices_host, int64_t co
 // The kind, then the target size, channels and copies: before any device work.
 static int pixel_args(mxv_handle *h, int32_t height, int32_t width, int32_t channels, int32_t copies) {
     const int32_t kind = render_env_id(h);
-    if (!renderable(kind))
+    if (!render_ready(h))
         return render_fail(h, MXV_ERR_UNSUPPORTED, "pixels: Pendulum-v1 draws an image asset (pendulum.py:228-244) that the engine does "
-                                                   "not carry: no frames for it");
+                                                   "not carry: no frames for it until the caller attaches one (mxv_render_attach_image)");
     if (channels != 1 && channels != 3) return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: channels must be 1 (gray) or 3 (RGB)");
     if (height < 1 || height > frame_h(kind) || width < 1 || width > frame_w(kind))
         return render_fail(h, MXV_ERR_INVALID_ARG, "pixels: height / width must lie in [1, frame height / width]");

@@ -34,20 +34,22 @@ class PixelRollout:
 
     def __init__(self, id: str, num_envs: int, *, height: int = 84, width: int = 84, grayscale: bool = True, stack: int = 4,
                  seed: int = 0, action_seed: int = 0, max_episode_steps: Optional[int] = None, device: int = 0,
-                 stream: Optional["torch.cuda.Stream"] = None):
+                 stream: Optional["torch.cuda.Stream"] = None, arrow_image=None):
         from .toy_text import TOY_TEXT_REGISTRY
 
         if id in TOY_TEXT_REGISTRY or id.startswith("Blackjack"):
             raise NotImplementedError(TOY_TEXT_REASON.format(id=id))
         kind = _spec(id).kind
-        if kind == _native.PENDULUM:
+        # Pendulum-v1: frames only with the caller's arrow image (pendulum.py:228-244); any other id refuses the keyword
+        arrow_image = _render.arrow_kwarg(kind, id, arrow_image)
+        if kind == _native.PENDULUM and arrow_image is None:
             raise NotImplementedError(_render.PENDULUM_REASON)
-        self.frame_shape = _render.pixel_shape(kind, height, width, grayscale)
+        self.frame_shape = _render.pixel_shape(kind, height, width, grayscale, (500, 500) if kind == _native.PENDULUM else None)
         if not isinstance(stack, int) or stack < 1:
             raise ValueError(f"stack must be a positive int, got {stack!r}")
         self.height, self.width, self.grayscale, self.stack = height, width, bool(grayscale), stack
         self.engine = DeviceRollout(id, num_envs, device=device, seed=seed, action_seed=action_seed,
-                                    max_episode_steps=max_episode_steps, autoreset=False, stream=stream)
+                                    max_episode_steps=max_episode_steps, autoreset=False, stream=stream, arrow_image=arrow_image)
         self.spec, self.num_envs, self.device, self.stream = self.engine.spec, self.engine.num_envs, self.engine.device, self.engine.stream
         self.single_observation_space = Box(0, 255, shape=(stack,) + self.frame_shape, dtype=np.uint8)
         self.observation_space = batch_space(self.single_observation_space, self.num_envs)

@@ -31,7 +31,12 @@ class DeviceRollout:
     def __init__(self, id: str, num_envs: int, *, device: int = 0, env_offset: int = 0, seed: int = 0,
                  action_seed: int = 0, max_episode_steps: Optional[int] = None, reward_f32: bool = False,
                  action_i32: bool = False, autoreset: bool = True, stream: Optional["torch.cuda.Stream"] = None,
-                 obs_carries_state: bool = False):
+                 obs_carries_state: bool = False, arrow_image=None):
+        if arrow_image is not None:
+            from . import _render
+
+            # Pendulum-v1's frames blit the caller's arrow image (an array or a PNG path; any other id refuses the keyword): checked first
+            arrow_image = _render.arrow_kwarg(_spec(id).kind, id, arrow_image)
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceRollout needs a HIP device (torch.cuda.is_available() is False); "
                                "gym_amd has no CPU fallback")
@@ -45,6 +50,10 @@ class DeviceRollout:
         self.handle = _native.Handle(self.spec.kind, num_envs, -1 if limit is None else int(limit), device=device,
                                      env_offset=env_offset, seed=seed, action_seed=action_seed, flags=flags)
         self.O, self.S, self.NA = self.handle.O, self.handle.S, self.handle.NA
+        if arrow_image is not None:      # render() / pixels() of Pendulum; the handle tracks last_u from here on (every env at None)
+            from . import _render
+
+            _render.attach_image(self.handle, arrow_image)
         # one torch-visible stream carries every launch of this handle: a stream of its own by default (rollouts then overlap the
         # learner's kernels and RCCL), or the caller's (`stream=`): a learner that steps with its own actions every iteration saves the
         # cross-stream wait of step() that way — ~6 us of GPU-side dependency latency per step, 18.8 instead of 25 us per 2^20-env
@@ -124,7 +133,7 @@ class DeviceRollout:
         outside [0, num_envs) yields an all-zero frame and an error at the next synchronising call."""
         from . import _render
 
-        H, W = _render.dims(self.spec.kind)
+        H, W = _render.frame_dims(self.handle)
         if indices is not None:
             assert indices.is_cuda and indices.dtype == torch.int32 and indices.is_contiguous() and indices.dim() == 1
         k = self.num_envs if indices is None else indices.numel()
@@ -144,7 +153,7 @@ class DeviceRollout:
         rounding).  `indices` / `out` / ordering / index errors as in render()."""
         from . import _render
 
-        shape = _render.pixel_shape(self.spec.kind, height, width, grayscale)
+        shape = _render.pixel_shape(self.spec.kind, height, width, grayscale, _render.frame_dims(self.handle))
         if indices is not None:
             assert indices.is_cuda and indices.dtype == torch.int32 and indices.is_contiguous() and indices.dim() == 1
         k = self.num_envs if indices is None else indices.numel()

@@ -290,7 +290,11 @@ class HipVectorEnv(VectorEnv):
         self._discrete = isinstance(action_space, Discrete)
         entropy = int.from_bytes(os.urandom(8), "little")  # Env.reset(seed=None) = fresh OS entropy (seeding.py:24)
         render_mode = kwargs.pop("render_mode", None)
-        if render_mode is not None:      # checked before any device work: "human" and Pendulum are refused without a GPU too
+        from . import _render
+
+        # Pendulum-v1's arrow image (pendulum.py:228-244): the caller's, checked here; any other id refuses the keyword
+        self._arrow_image = _render.arrow_kwarg(self.kind, id, kwargs.pop("arrow_image", None))
+        if render_mode is not None:      # checked before any device work: "human" and Pendulum without arrow_image are refused without a GPU too
             self._enable_render(render_mode)
         # autoreset=False (MXV_FLAG_NO_AUTORESET): dynamics + TimeLimit only, a finished env stays finished until reset() — the single-env
         # contract of gym.Env (gym/core.py:75-184), which gym_amd.single_env.HipEnv builds on
@@ -298,6 +302,8 @@ class HipVectorEnv(VectorEnv):
         self._handle = _native.Handle(self.kind, num_envs, self._max_episode_steps, device=device,
                                       env_offset=env_offset, seed=entropy, action_seed=entropy ^ 0x9E3779B97F4A7C15,
                                       **({} if autoreset else {"flags": _native.FLAG_NO_AUTORESET}))
+        if self._arrow_image is not None:
+            _render.attach_image(self._handle, self._arrow_image)
         self._actions = None
         self._was_reset = False
         self._per_env = False  # True while sub-envs hold differing physics attributes (set_attr with a list)
@@ -318,6 +324,8 @@ class HipVectorEnv(VectorEnv):
             raise ValueError(f"render_mode={render_mode!r} is not supported by the device engine: it draws frames as arrays, "
                              "use render_mode='rgb_array' (or 'rgb_array_list' through gym.make); 'human' needs a window")
         fps = _render.RENDER_FPS.get(self.kind)
+        if fps is None and self._arrow_image is not None:
+            fps = _render.PENDULUM_RENDER_FPS
         if fps is None:
             raise NotImplementedError(_render.PENDULUM_REASON)
         self.render_mode = "rgb_array"
@@ -611,6 +619,10 @@ class HipVectorEnv(VectorEnv):
         self._handle = _native.Handle(snap["env_id"], snap["num_envs"], snap["max_episode_steps"], device=device,
                                       env_offset=snap["env_offset"], seed=snap["base_seed"], action_seed=snap["action_seed"],
                                       flags=snap["flags"])
+        if self.__dict__.get("_arrow_image") is not None:   # Pendulum frames: the image travels in the pickle, last_u in the snapshot
+            from . import _render
+
+            _render.attach_image(self._handle, self._arrow_image)
         self._handle.restore(snap)
         self._packed = bool(self._handle.final_packed(True))
         self._own_arrays = self.copy or self._packed

@@ -6,7 +6,15 @@
  * continuous_mountain_car.py:191-292) — the same primitives, integer coordinates, colours and draw order — rasterised by the engine's
  * own integer rule (4 x 4 samples per pixel, coverage blend, 1-px lines), flipped vertically: uint8 [H][W][3] RGB, row 0
  * at the top, the layout of the reference's np.transpose(pixels3d(screen), (1, 0, 2)).  CartPole / MountainCar*: 400 x 600,
- * Acrobot: 500 x 500.  Pendulum (its frame blits an image asset) and the toy_text engines have no frame: MXV_ERR_UNSUPPORTED. */
+ * Acrobot: 500 x 500.  The toy_text engines have no frame: MXV_ERR_UNSUPPORTED.
+ *
+ * Pendulum-v1 (pendulum.py:167-261, 500 x 500) blits an image asset, the torque arrow (assets/clockwise.png), which the engine does not
+ * carry: the caller supplies it (mxv_render_attach_image).  Until then every frame and pixel call on a Pendulum handle returns
+ * MXV_ERR_UNSUPPORTED, and so does the handle-free mxv_render_dims(MXV_PENDULUM).  With an image attached the handle also tracks the
+ * reference's render state `last_u` per env: NaN (= None) after a reset (mxv_reset, masked or not, mxv_reset_host, an autoreset inside a
+ * step), else the float32 clip of the env's last action to [-max_torque, max_torque] (the step's own clip, pendulum.py:127-128); a NaN
+ * action leaves NaN, and then no arrow is drawn (the reference raises there).  mxv_set_state leaves it unchanged.  The arrow is an
+ * MXV_RENDER_BLIT record rasterised by the engine's own rule (below), not SDL's smoothscale / blend. */
 #ifndef MXV_RENDER_H
 #define MXV_RENDER_H
 
@@ -33,11 +41,31 @@ enum {
     MXV_RENDER_HLINE = 5,
     MXV_RENDER_VLINE = 6,
     MXV_RENDER_LINE = 7,
-    MXV_RENDER_AALINE = 8
+    MXV_RENDER_AALINE = 8,
+    /* (op, 0, 0, 0, x, y, w, h, flip_x, flip_y, 0, 0) in whole surface pixels (y before the final flip): surface pixel (px, py) with
+     * 0 <= py - y < h, 0 <= px - x < w shows the scaled image's pixel (r, c) = (py - y, px - x), r -> h - 1 - r when flip_y and
+     * c -> w - 1 - c when flip_x.  That pixel is the rounded mean (sum + n / 2) / n of each straight-RGBA channel over the n source
+     * pixels of rows [floor(r Hs / h), ceil((r + 1) Hs / h)) and columns likewise (Hs x Ws the attached image), and it is blended as
+     * d' = (s a + d (255 - a) + 127) / 255 per RGB channel, a its mean alpha.  w = 0 draws nothing. */
+    MXV_RENDER_BLIT = 9
 };
 
 /* Frame height and width of an env kind.  MXV_ERR_UNSUPPORTED for Pendulum, MXV_ERR_INVALID_ARG for an unknown kind or NULL outputs. */
 int mxv_render_dims(int32_t env_id, int32_t *height, int32_t *width);
+
+/* Frame height and width of a handle: mxv_render_dims of its kind, and 500 x 500 for a Pendulum handle with an image attached
+ * (MXV_ERR_UNSUPPORTED without one). */
+int mxv_render_frame_dims(mxv_handle *h, int32_t *height, int32_t *width);
+
+/* Pendulum handles only (MXV_ERR_UNSUPPORTED for any other kind): copies the arrow image, uint8 [height][width][4] straight RGBA in host
+ * memory (1 <= height, width <= 1024), to the device and builds its summed-area table there; every env's last_u becomes NaN (None).
+ * Calling it again replaces the image.  Synchronises the handle's stream; not recordable into a hipGraph. */
+int mxv_render_attach_image(mxv_handle *h, const uint8_t *rgba_host, int32_t height, int32_t width);
+
+/* last_u of every env, float32 [N] in host memory, NaN = None (checkpoints).  MXV_ERR_UNSUPPORTED without an attached image.  Both
+ * synchronise the handle's stream. */
+int mxv_render_get_torques_host(mxv_handle *h, float *last_u_host);
+int mxv_render_set_torques_host(mxv_handle *h, const float *last_u_host);
 
 /* Renders `count` frames of the handle's current states into frames_dev (uint8 [count][H][W][3], device, 16-byte aligned): frame k
  * shows env indices_dev[k] (int32, device; repeats allowed), or env k when indices_dev is NULL (then count <= N).  Physics attributes
@@ -65,7 +93,8 @@ int mxv_render_scene_host(mxv_handle *h, const int32_t *indices_host, int64_t co
  * PixelObservationWrapper -> GrayScaleObservation -> ResizeObservation (pixel_observation.py:165-190, gray_scale_observation.py:50-64,
  * resize_observation.py:48-70).  Attributes, indices, errors and stream order are those of mxv_render.  Argument errors (height /
  * width out of range, channels not 1 or 3, copies < 1, NULL outputs, strides below one observation, a misaligned output or index
- * pointer of mxv_pixels) return MXV_ERR_INVALID_ARG, and Pendulum MXV_ERR_UNSUPPORTED, before the device is touched. */
+ * pointer of mxv_pixels) return MXV_ERR_INVALID_ARG, and Pendulum without an attached image MXV_ERR_UNSUPPORTED, before the device is
+ * touched. */
 
 /* Observations of `count` envs into out_dev (uint8 [count][height][width][channels], device, 16-byte aligned): observation k shows
  * env indices_dev[k] (int32, device; repeats allowed), or env k when indices_dev is NULL (then count <= N). */
