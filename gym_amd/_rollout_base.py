@@ -1,0 +1,64 @@
+"""What the device-resident front ends share (DeviceRollout, TabularRollout, BlackjackRollout): the device check, the engine's
+stream, the ordering calls and the allocation of trajectory tensors.  torch is imported when a rollout is constructed, not with this
+module: gym_amd.toy_text stays importable without it."""
+from __future__ import annotations
+
+from . import _native
+
+
+class _RolloutBase:
+    # what synchronize() raises for an out-of-range action latched by a step: None lets the engine's MxvError through
+    invalid_action_error = None
+
+    def __init__(self, num_envs: int, device: int):
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device (torch.cuda.is_available() is False); "
+                               "gym_amd has no CPU fallback")
+        self._torch = torch
+        self.num_envs = int(num_envs)
+        self.device = torch.device("cuda", device)
+        self.last_placement = None      # the report of the last sorted / placed trajectory_buffers()
+
+    def _adopt(self, handle, stream=None):
+        """One torch-visible stream carries every launch of `handle`: the caller's (`stream`) or one of its own."""
+        self.handle = handle
+        self.stream = stream if stream is not None else self._torch.cuda.Stream(device=self.device)
+        handle.set_stream(self.stream.cuda_stream)
+
+    def _allocate(self, specs, layout: str, classes: dict, auto_bytes: int, sorted_min_bytes: int, budget_bytes=None):
+        """The tensors of `specs` — (name, shape, dtype, zero-filled) each — as a dict.  layout="sorted": ordinary allocations sorted by HBM
+        class (gym_amd/placement.py), `classes` naming the class of every write stream, the report left in self.last_placement;
+        "separate": one torch allocation per tensor; "auto": sorted once `auto_bytes` reaches `sorted_min_bytes`."""
+        t = self._torch
+        if layout == "auto":
+            from . import placement
+
+            layout = "sorted" if auto_bytes >= sorted_min_bytes and placement.enabled() else "separate"   # MXV_PLACEMENT=off: never sort
+        if layout == "sorted":
+            from .placement import sorted_tensors
+
+            out, self.last_placement = sorted_tensors(specs, classes, self.device, self.stream, budget_bytes)
+            return out
+        if layout != "separate":
+            raise ValueError(f"layout must be 'auto', 'sorted' or 'separate', got {layout!r}")
+        with t.cuda.stream(self.stream):
+            return {name: (t.zeros if zero else t.empty)(shape, dtype=dt, device=self.device) for name, shape, dt, zero in specs}
+
+    def ready(self):
+        """GPU-side ordering of the outputs: the caller's current torch stream waits for everything launched so far on the
+        engine's stream (no host synchronisation).  Use before touching output tensors outside `with torch.cuda.stream(r.stream)`."""
+        self._torch.cuda.current_stream(self.device).wait_stream(self.stream)
+
+    def synchronize(self):
+        """Wait for the engine's stream; raises if a step saw an out-of-range action."""
+        try:
+            self.handle.sync()
+        except _native.MxvError as e:
+            if e.code == _native.ERR_INVALID_ACTION and self.invalid_action_error is not None:
+                raise self.invalid_action_error(e.message) from None
+            raise
+
+    def close(self):
+        self.handle.close()

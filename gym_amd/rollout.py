@@ -21,13 +21,16 @@ from typing import Optional
 import torch
 
 from . import _native
+from ._rollout_base import _RolloutBase
 from .registration import spec as _spec
 
 
 MODES = {"eager": _native.ROLLOUT_EAGER, "graph": _native.ROLLOUT_GRAPH, "fused": _native.ROLLOUT_FUSED}
 
 
-class DeviceRollout:
+class DeviceRollout(_RolloutBase):
+    invalid_action_error = AssertionError      # what the reference's step() raises (Discrete.contains)
+
     def __init__(self, id: str, num_envs: int, *, device: int = 0, env_offset: int = 0, seed: int = 0,
                  action_seed: int = 0, max_episode_steps: Optional[int] = None, reward_f32: bool = False,
                  action_i32: bool = False, autoreset: bool = True, stream: Optional["torch.cuda.Stream"] = None,
@@ -37,29 +40,23 @@ class DeviceRollout:
 
             # Pendulum-v1's frames blit the caller's arrow image (an array or a PNG path; any other id refuses the keyword): checked first
             arrow_image = _render.arrow_kwarg(_spec(id).kind, id, arrow_image)
-        if not torch.cuda.is_available():
-            raise RuntimeError("DeviceRollout needs a HIP device (torch.cuda.is_available() is False); "
-                               "gym_amd has no CPU fallback")
+        super().__init__(num_envs, device)
         self.spec = _spec(id)
-        self.num_envs = int(num_envs)
-        self.device = torch.device("cuda", device)
         limit = self.spec.max_episode_steps if max_episode_steps is None else max_episode_steps
         flags = (_native.FLAG_REWARD_F32 if reward_f32 else 0) | (_native.FLAG_ACTION_I32 if action_i32 else 0)
         if not autoreset:
             flags |= _native.FLAG_NO_AUTORESET
-        self.handle = _native.Handle(self.spec.kind, num_envs, -1 if limit is None else int(limit), device=device,
-                                     env_offset=env_offset, seed=seed, action_seed=action_seed, flags=flags)
+        # one torch-visible stream carries every launch of this handle: a stream of its own by default (rollouts then overlap the
+        # learner's kernels and RCCL), or the caller's (`stream=`): a learner that steps with its own actions every iteration saves the
+        # cross-stream wait of step() that way — ~6 us of GPU-side dependency latency per step, 18.8 instead of 25 us per 2^20-env
+        # CartPole step (bench.py variants.step_loop; `with torch.cuda.stream(r.stream):` around the loop does the same)
+        self._adopt(_native.Handle(self.spec.kind, num_envs, -1 if limit is None else int(limit), device=device,
+                                   env_offset=env_offset, seed=seed, action_seed=action_seed, flags=flags), stream)
         self.O, self.S, self.NA = self.handle.O, self.handle.S, self.handle.NA
         if arrow_image is not None:      # render() / pixels() of Pendulum; the handle tracks last_u from here on (every env at None)
             from . import _render
 
             _render.attach_image(self.handle, arrow_image)
-        # one torch-visible stream carries every launch of this handle: a stream of its own by default (rollouts then overlap the
-        # learner's kernels and RCCL), or the caller's (`stream=`): a learner that steps with its own actions every iteration saves the
-        # cross-stream wait of step() that way — ~6 us of GPU-side dependency latency per step, 18.8 instead of 25 us per 2^20-env
-        # CartPole step (bench.py variants.step_loop; `with torch.cuda.stream(r.stream):` around the loop does the same)
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
-        self.handle.set_stream(self.stream.cuda_stream)
         self.reward_dtype = torch.float32 if reward_f32 else torch.float64
         if self.NA > 0:
             self.action_dtype = torch.int32 if action_i32 else torch.int64
@@ -257,7 +254,7 @@ class DeviceRollout:
         of that step is set (what a learner bootstraps from when an episode was truncated), other rows keep their content.
 
         layout="sorted" (what "auto" picks for sets of 1 GiB and more): ordinary allocations, but the reward / action tensors are
-        made to lie in another third of the HBM address space than the observations (_sorted_buffers): the write-bound rollout then
+        made to lie in another third of the HBM address space than the observations (gym_amd/placement.py): the write-bound rollout then
         runs in its fast mode by construction instead of one time in three; the report is left in
         `self.last_placement`.  The search holds extra device memory while it runs (typically a few GiB for 0.1 s): at most
         `max_park_bytes` (default: half of what is free beyond the set and at most 8 GiB whenever anybody else holds device memory or this
@@ -290,16 +287,9 @@ class DeviceRollout:
         specs += [("obs", (K, n, self.O), torch.float32, False), ("reward", (K, n), self.reward_dtype, False),
                   ("terminated", (K, n), torch.uint8, False), ("truncated", (K, n), torch.uint8, False),
                   ("actions", (K, n), self.action_dtype, False)]
-        if layout == "auto":
-            total = sum(math.prod(shape) * torch.empty((), dtype=dt).element_size() for _, shape, dt, _ in specs)
-            from . import placement
-
-            layout = "sorted" if total >= _native.SORTED_MIN_BYTES and placement.enabled() else "separate"   # MXV_PLACEMENT=off: never sort
-        if layout == "sorted":
-            return self._sorted_buffers(specs, max_park_bytes)
+        group = {"obs": 0, "reward": 1, "actions": 1}
         if layout == "placed":
             npdt = {torch.float32: "<f4", torch.float64: "<f8", torch.int32: "<i4", torch.int64: "<i8", torch.uint8: "|u1"}
-            group = {"obs": 0, "reward": 1, "actions": 1}
             mem = _native.PlacedMemory(dev.index, [(name, shape, npdt[dt], group.get(name, -1)) for name, shape, dt, _ in specs])
             self.last_placement = mem.info
             out = mem.tensors()
@@ -308,19 +298,11 @@ class DeviceRollout:
                     if zero:
                         out[name].zero_()
             return out
-        with torch.cuda.stream(self.stream):
-            if layout == "separate":
-                return {name: (torch.zeros if zero else torch.empty)(shape, dtype=dt, device=dev) for name, shape, dt, zero in specs}
+        if layout not in ("auto", "sorted", "separate"):
             raise ValueError(f"layout must be 'auto', 'sorted', 'placed' or 'separate', got {layout!r}")
-
-    def _sorted_buffers(self, specs, budget_bytes: Optional[int] = None):
-        """Ordinary (torch / hipMalloc) tensors, SORTED by HBM class (gym_amd/placement.py): observations on one class, rewards +
-        actions — the same bytes per env-step for CartPole — on another; the report is left in self.last_placement."""
-        from .placement import sorted_tensors
-
-        out, report = sorted_tensors(specs, {"obs": 0, "reward": 1, "actions": 1}, self.device, self.stream, budget_bytes)
-        self.last_placement = report
-        return out
+        # sorted: observations on one HBM class, rewards + actions — the same bytes per env-step for CartPole — on another
+        total = sum(math.prod(shape) * torch.empty((), dtype=dt).element_size() for _, shape, dt, _ in specs)
+        return self._allocate(specs, layout, group, total, _native.SORTED_MIN_BYTES, max_park_bytes)
 
     def state_dict(self) -> dict:
         """Snapshot (NumPy arrays and ints, picklable) from which load_state_dict() continues bit-identically: env state,
@@ -407,19 +389,3 @@ class DeviceRollout:
         self.handle.sample_actions(self.actions)
         return self.actions
 
-    def ready(self):
-        """GPU-side ordering of the outputs: the caller's current torch stream waits for everything launched so far on the
-        engine's stream (no host synchronisation).  Use before touching output tensors outside `with torch.cuda.stream(r.stream)`."""
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
-
-    def synchronize(self):
-        """Wait for the engine's stream; raises if a step saw an out-of-range action."""
-        try:
-            self.handle.sync()
-        except _native.MxvError as e:
-            if e.code == _native.ERR_INVALID_ACTION:
-                raise AssertionError(e.message) from None
-            raise
-
-    def close(self):
-        self.handle.close()

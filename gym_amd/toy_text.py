@@ -13,15 +13,15 @@ VectorEnv._add_info (vector_env.py:208-258: an info array takes the type of the 
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
 from . import _native, error
+from ._rollout_base import _RolloutBase
 from .spaces import Discrete
-from .vector_env import LazyInfos, VectorEnv, _Pending
+from .vector_env import LazyInfos, _EngineVectorEnv, _Pending, _object_array, _seed_pair, _set_final_infos
 
 __all__ = ["TabularMDP", "generate_random_map", "frozen_lake_mdp", "taxi_mdp", "cliff_walking_mdp", "HipTabularVectorEnv", "TabularRollout",
            "HipBlackjackVectorEnv", "BlackjackRollout", "TOY_TEXT_REGISTRY", "taxi_encode", "taxi_decode"]
@@ -283,11 +283,10 @@ def _make_handle(mdp: TabularMDP, num_envs: int, limit: Optional[int], device: i
                        env_offset=env_offset, seed=seed, action_seed=action_seed, compact=compact, general_kernel=general_kernel)
 
 
-class HipTabularVectorEnv(VectorEnv):
+class HipTabularVectorEnv(_EngineVectorEnv):
     """`num_envs` copies of one tabular toy_text env on one MI355X, with SyncVectorEnv's call surface and return contract."""
 
-    metadata = {"render_modes": []}
-    render_mode = None
+    _transient = ("spec", "_tt_spec")
 
     def __init__(self, id: str, num_envs: int = 1, *, device: int = 0, max_episode_steps: Optional[int] = None,
                  env_offset: int = 0, **kwargs):
@@ -295,39 +294,32 @@ class HipTabularVectorEnv(VectorEnv):
         # (gym/envs/registration.py:657).  The engine's own registry entry therefore lives in a private attribute and is what
         # call() / pickling use.
         self.spec = self._tt_spec = _spec(id)
-        if kwargs.pop("render_mode", None) is not None:
-            raise TypeError(f"{id}: the device engine does not render (render_mode must be None)")
+        self._refuse_render_mode(id, kwargs)
         for k in kwargs:
             if k not in self.spec.kwargs:
                 raise TypeError(f"{id} got an unexpected keyword argument {k!r}")
         self.mdp = self.spec.build(**kwargs)
         super().__init__(num_envs, Discrete(self.mdp.num_states), Discrete(self.mdp.num_actions))
         limit = self.spec.max_episode_steps if max_episode_steps is None else max_episode_steps
-        entropy = int.from_bytes(os.urandom(8), "little")
-        self._handle = _make_handle(self.mdp, num_envs, limit, device, env_offset, entropy, entropy ^ 0x9E3779B97F4A7C15)
-        self._limit, self._env_offset = limit, env_offset
-        self._actions = None
-        self._was_reset = False
+        self._device, self._limit, self._env_offset = device, limit, env_offset
+        self._handle = self._open_handle(*_seed_pair())
 
-    # -- pickling (the reference's checkpoint: tests/envs/test_envs.py:192-200) ----------------------------------------
+    def _open_handle(self, seed, action_seed):
+        return _make_handle(self.mdp, self.num_envs, self._limit, self._device, self._env_offset, seed, action_seed)
+
+    # -- pickling: the registry entry holds the (unpicklable) builder, its id travels instead ---------------------------
     def __getstate__(self):
-        self._assert_is_running()
-        d = {k: v for k, v in self.__dict__.items() if k not in ("_handle", "spec", "_tt_spec")}
-        d["_spec_id"] = self._tt_spec.id           # the registry entry holds the (unpicklable) builder
+        d = super().__getstate__()
+        d["_spec_id"] = self._tt_spec.id
         if self.spec is not self._tt_spec:
             d["_outer_spec"] = self.spec           # e.g. gym's EnvSpec after gym.make("hip/<id>")
-        d["_snapshot"] = self._handle.snapshot()
-        d["_ctor"] = (self._handle.device, self._limit, self._env_offset)
         return d
 
     def __setstate__(self, d):
         d = dict(d)
-        snap, (device, limit, env_offset) = d.pop("_snapshot"), d.pop("_ctor")
         self._tt_spec = _spec(d.pop("_spec_id"))
         self.spec = d.pop("_outer_spec", self._tt_spec)
-        self.__dict__.update(d)
-        self._handle = _make_handle(self.mdp, self.num_envs, limit, device, env_offset, snap["base_seed"], snap["action_seed"])
-        self._handle.restore(snap)
+        super().__setstate__(d)
 
     # -- infos ---------------------------------------------------------------------------------------------------
     def _mask_info(self, infos, states):
@@ -335,32 +327,12 @@ class HipTabularVectorEnv(VectorEnv):
             return
         table, n = self.mdp.action_mask, self.num_envs
 
-        def build():
-            arr = np.full(n, None, dtype=object)   # type(np.ndarray) is not numeric -> object array (vector_env.py:248-253)
-            for i in range(n):
-                arr[i] = table[states[i]].copy()
-            return arr
-
-        dict.__setitem__(infos, "action_mask", _Pending(build))
+        # type(np.ndarray) is not numeric -> object array (vector_env.py:248-253)
+        dict.__setitem__(infos, "action_mask", _Pending(lambda: _object_array(n, range(n), lambda i: table[states[i]].copy())))
         dict.__setitem__(infos, "_action_mask", np.ones(n, dtype=bool))
 
-    def reset_wait(self, seed: Optional[Union[int, List[int]]] = None, options: Optional[dict] = None):
-        self._assert_is_running()
-        if seed is not None:
-            if isinstance(seed, (int, np.integer)):
-                if seed < 0:
-                    raise error.Error(f"Seed must be a non-negative integer or omitted, not {seed}")
-                self._handle.seed(int(seed), None)
-            else:
-                seeds = list(seed)
-                assert len(seeds) == self.num_envs
-                for s in seeds:
-                    if not (isinstance(s, (int, np.integer)) and s >= 0):
-                        raise error.Error(f"Seed must be a non-negative integer or omitted, not {s}")
-                self._handle.seed(0, np.array(seeds, dtype=np.uint64))
+    def _reset(self, options):
         obs = self._handle.reset_host()
-        self._was_reset = True
-        self._actions = None
         infos = LazyInfos()
         one = np.int64 if self.mdp.reset_prob_is_int else np.float64
         dict.__setitem__(infos, "prob", np.ones(self.num_envs, dtype=one))
@@ -369,30 +341,18 @@ class HipTabularVectorEnv(VectorEnv):
         return obs, infos
 
     # -- step ------------------------------------------------------------------------------------------------------
-    def step_async(self, actions):
-        self._assert_is_running()
-        if self._actions is not None:
-            raise error.AlreadyPendingCallError("Calling `step_async` while waiting for a pending call to `step` to "
-                                                "complete.", "step")
+    def _check_actions(self, actions):
         a = np.asarray(actions)
         if a.shape != (self.num_envs,) or not np.issubdtype(a.dtype, np.integer):
             raise KeyError(f"{actions!r} is not a batch of {self.num_envs} integer actions")
-        self._actions = np.ascontiguousarray(a, dtype=np.int64)
+        return np.ascontiguousarray(a, dtype=np.int64)
 
-    def step_wait(self):
-        self._assert_is_running()
-        if self._actions is None:
-            raise error.NoAsyncCallError("Calling `step_wait` without any prior call to `step_async`.", "step")
-        actions, self._actions = self._actions, None
-        if not self._was_reset:
-            raise error.ResetNeeded("Cannot call env.step() before calling env.reset()")
-        try:
-            obs, rew, term, trunc, prob, fin, fprob = self._handle.step_host(actions, pooled=True)
-        except _native.MxvError as e:
-            if e.code == _native.ERR_INVALID_ACTION:
-                bad = actions[(actions < 0) | (actions >= self.mdp.num_actions)]
-                raise KeyError(int(bad[0]) if bad.size else actions) from None   # the reference: P[s][a] -> KeyError
-            raise
+    def _invalid_action(self, actions):
+        bad = actions[(actions < 0) | (actions >= self.mdp.num_actions)]
+        return KeyError(int(bad[0]) if bad.size else actions)   # the reference: P[s][a] -> KeyError
+
+    def _step(self, actions):
+        obs, rew, term, trunc, prob, fin, fprob = self._handle.step_host(actions, pooled=True)
         n = self.num_envs
         done = term | trunc
         infos = LazyInfos()
@@ -406,20 +366,15 @@ class HipTabularVectorEnv(VectorEnv):
         if done.any():
             idx = np.flatnonzero(done)
             mask_table = self.mdp.action_mask
-            dict.__setitem__(infos, "final_observation", np.where(done, fin, 0).astype(np.int64))  # python ints -> int array
-            dict.__setitem__(infos, "_final_observation", done.copy())
 
-            def build_final_info():
-                arr = np.full(n, None, dtype=object)
-                for i in idx:
-                    d = {"prob": float(fprob[i])}
-                    if mask_table is not None:
-                        d["action_mask"] = mask_table[fin[i]].copy()
-                    arr[i] = d
-                return arr
+            def final_info(i):
+                d = {"prob": float(fprob[i])}
+                if mask_table is not None:
+                    d["action_mask"] = mask_table[fin[i]].copy()
+                return d
 
-            dict.__setitem__(infos, "final_info", _Pending(build_final_info))
-            dict.__setitem__(infos, "_final_info", done.copy())
+            _set_final_infos(infos, done, np.where(done, fin, 0).astype(np.int64),   # python ints -> int array
+                             _Pending(lambda: _object_array(n, idx, final_info)))
         return obs, rew, term, trunc, infos
 
     # -- attribute access of the sub-envs (P, desc-free: the MDP tables) ---------------------------------------------
@@ -445,47 +400,23 @@ class HipTabularVectorEnv(VectorEnv):
             return tuple(self.mdp.action_mask[int(state)].copy() for _ in range(self.num_envs))
         raise AttributeError(f"{self._tt_spec.id} sub-environments have no attribute {name!r}")
 
-    def close_extras(self, **kwargs):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            h.close()
 
-    def _assert_is_running(self):
-        if self.closed:
-            raise error.ClosedEnvironmentError(f"Trying to operate on `{type(self).__name__}`, after a call to `close()`.")
-
-    @property
-    def unwrapped(self):
-        return self
-
-    @property
-    def handle(self) -> "_native.Tab":
-        return self._handle
-
-
-class TabularRollout:
+class TabularRollout(_RolloutBase):
     """Device-resident front-end: K sampled steps per launch into [K, N] torch tensors (obs / actions int64, reward / prob
     float64, terminated / truncated uint8), state resident on the device between calls.  compact=True: the trajectory tensors hold the
     contract dtypes of SURVEY.md §8(d) — int32 obs / actions, float32 reward / prob: 18 instead of 34 bytes per env-step, same values."""
 
     def __init__(self, id: str, num_envs: int, *, device: int = 0, env_offset: int = 0, seed: int = 0, action_seed: int = 0,
                  max_episode_steps: Optional[int] = None, compact: bool = False, general_kernel: bool = False, **kwargs):
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("TabularRollout needs a HIP device; gym_amd has no CPU fallback")
-        self._torch = torch
+        super().__init__(num_envs, device)
+        torch = self._torch
         self.spec = _spec(id)
         self.mdp = self.spec.build(**kwargs)
-        self.num_envs = int(num_envs)
-        self.device = torch.device("cuda", device)
         limit = self.spec.max_episode_steps if max_episode_steps is None else max_episode_steps
         self.compact = bool(compact)
         self.int_dtype, self.real_dtype = (torch.int32, torch.float32) if compact else (torch.int64, torch.float64)
-        self.handle = _make_handle(self.mdp, num_envs, limit, device, env_offset, seed, action_seed, compact=compact,
-                                   general_kernel=general_kernel)
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.handle.set_stream(self.stream.cuda_stream)
+        self._adopt(_make_handle(self.mdp, num_envs, limit, device, env_offset, seed, action_seed, compact=compact,
+                                 general_kernel=general_kernel))
         with torch.cuda.stream(self.stream):
             self.obs = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
         self.stream.synchronize()
@@ -502,24 +433,11 @@ class TabularRollout:
         the launch writes four 8-byte streams, and it runs 5.7 / 6.1 / 7.1 us per 2^20-env step with them split 2 + 2 / 1 + 3 / 4 + 0
         over two classes (profiles/r3/r3g_tab_class_ab.jsonl) — obs + reward on one, actions + prob on another.  layout="separate":
         ordinary allocations.  The report is left in self.last_placement."""
-        t, n, dev = self._torch, self.num_envs, self.device
+        t, n = self._torch, self.num_envs
         it, rt = self.int_dtype, self.real_dtype
         specs = [("obs", (K, n), it, False), ("reward", (K, n), rt, False), ("actions", (K, n), it, False),
                  ("prob", (K, n), rt, False), ("terminated", (K, n), t.uint8, False), ("truncated", (K, n), t.uint8, False)]
-        if layout == "auto":
-            from . import placement
-
-            stored = 18 if self.compact else 34
-            layout = "sorted" if stored * K * n >= (2 << 30) and placement.enabled() else "separate"     # MXV_PLACEMENT=off: never sort
-        if layout == "sorted":
-            from .placement import sorted_tensors
-
-            out, self.last_placement = sorted_tensors(specs, {"obs": 0, "reward": 0, "actions": 1, "prob": 1}, dev, self.stream)
-            return out
-        if layout != "separate":
-            raise ValueError(f"layout must be 'auto', 'sorted' or 'separate', got {layout!r}")
-        with t.cuda.stream(self.stream):
-            return {name: t.empty(shape, dtype=dt, device=dev) for name, shape, dt, _ in specs}
+        return self._allocate(specs, layout, {"obs": 0, "reward": 0, "actions": 1, "prob": 1}, (18 if self.compact else 34) * K * n, 2 << 30)
 
     def rollout_per_step(self, K: int, out: Optional[dict] = None):
         out = self.trajectory_buffers(K) if out is None else out
@@ -537,18 +455,8 @@ class TabularRollout:
         out["actions"] = actions
         return out
 
-    def ready(self):
-        """The caller's current torch stream waits (on the GPU) for everything launched on the engine's stream."""
-        self._torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
-    def synchronize(self):
-        self.handle.sync()
-
-    def close(self):
-        self.handle.close()
-
-
-class BlackjackRollout:
+class BlackjackRollout(_RolloutBase):
     """Device-resident front-end of the Blackjack engine (mxv_bj_*): K sampled steps per launch into [K, ...] torch tensors — obs
     [K, 3, N] (player total, dealer's first card, usable ace), actions [K, N], reward [K, N], terminated / truncated uint8 [K, N] — with
     the hands resident on the device between calls.  compact=True: int32 observations / actions and float32 rewards (the contract dtypes
@@ -556,23 +464,15 @@ class BlackjackRollout:
 
     def __init__(self, num_envs: int, *, device: int = 0, env_offset: int = 0, seed: int = 0, action_seed: int = 0, natural: bool = False,
                  sab: bool = True, max_episode_steps: Optional[int] = None, compact: bool = False):
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("BlackjackRollout needs a HIP device; gym_amd has no CPU fallback")
-        self._torch = torch
-        self.num_envs = int(num_envs)
-        self.device = torch.device("cuda", device)
+        super().__init__(num_envs, device)
+        torch = self._torch
         self.compact = bool(compact)
         self.int_dtype, self.real_dtype = (torch.int32, torch.float32) if compact else (torch.int64, torch.float64)
-        self.handle = _native.Blackjack(self.num_envs, natural=natural, sab=sab, device=device, env_offset=env_offset, seed=seed,
-                                        action_seed=action_seed, max_episode_steps=-1 if max_episode_steps is None else max_episode_steps)
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.handle.set_stream(self.stream.cuda_stream)
+        self._adopt(_native.Blackjack(self.num_envs, natural=natural, sab=sab, device=device, env_offset=env_offset, seed=seed,
+                                      action_seed=action_seed, max_episode_steps=-1 if max_episode_steps is None else max_episode_steps))
         with torch.cuda.stream(self.stream):
             self.obs = torch.zeros((3, self.num_envs), dtype=torch.int64, device=self.device)
         self.stream.synchronize()
-        self.last_placement = None
 
     def reset(self, seed: Optional[int] = None):
         if seed is not None:
@@ -585,25 +485,13 @@ class BlackjackRollout:
         """Output tensors of rollout_per_step.  Sets of 2 GiB and more ("auto") are sorted by HBM class (gym_amd/placement.py): the launch
         writes five 8-byte (4-byte) streams — the three observation columns on one class, rewards + actions on another.  The report is left
         in self.last_placement."""
-        t, n, dev = self._torch, self.num_envs, self.device
+        t, n = self._torch, self.num_envs
         it, rt = self.int_dtype, self.real_dtype
         specs = [("obs", (K, 3, n), it, False), ("reward", (K, n), rt, False), ("actions", (K, n), it, False),
                  ("terminated", (K, n), t.uint8, False), ("truncated", (K, n), t.uint8, False)]
         if want_final:
             specs.append(("final_obs", (K, 3, n), it, True))
-        if layout == "auto":
-            from . import placement
-
-            layout = "sorted" if (22 if self.compact else 42) * K * n >= (2 << 30) and placement.enabled() else "separate"
-        if layout == "sorted":
-            from .placement import sorted_tensors
-
-            out, self.last_placement = sorted_tensors(specs, {"obs": 0, "reward": 1, "actions": 1}, dev, self.stream)
-            return out
-        if layout != "separate":
-            raise ValueError(f"layout must be 'auto', 'sorted' or 'separate', got {layout!r}")
-        with t.cuda.stream(self.stream):
-            return {name: (t.zeros if zero else t.empty)(shape, dtype=dt, device=dev) for name, shape, dt, zero in specs}
+        return self._allocate(specs, layout, {"obs": 0, "reward": 1, "actions": 1}, (22 if self.compact else 42) * K * n, 2 << 30)
 
     def rollout_per_step(self, K: int, out: Optional[dict] = None):
         out = self.trajectory_buffers(K) if out is None else out
@@ -623,141 +511,56 @@ class BlackjackRollout:
             out["actions"][:K].copy_(actions)      # a tape-driven launch records no actions: the returned set still holds the ones that were played
         return out
 
-    def ready(self):
-        """The caller's current torch stream waits (on the GPU) for everything launched on the engine's stream."""
-        self._torch.cuda.current_stream(self.device).wait_stream(self.stream)
-
-    def synchronize(self):
-        self.handle.sync()
-
-    def close(self):
-        self.handle.close()
-
 
 # ---- Blackjack-v1 (gym/envs/toy_text/blackjack.py): not a P table — its own kernel (gym_amd/csrc/mxv_bj.hip) ---------------
-class HipBlackjackVectorEnv(VectorEnv):
+class HipBlackjackVectorEnv(_EngineVectorEnv):
     """`num_envs` Blackjack tables on one MI355X with SyncVectorEnv's contract: observations are a tuple of three int64
     arrays (player total, dealer's showing card, usable ace) — batch_space(Tuple(Discrete(32), Discrete(11), Discrete(2)));
     rewards float64; infos empty except `final_observation` (object array of (int, int, bool) tuples) / `final_info`."""
-
-    metadata = {"render_modes": []}
-    render_mode = None
 
     def __init__(self, id: str = "Blackjack-v1", num_envs: int = 1, *, device: int = 0, natural: bool = False, sab: bool = True,
                  max_episode_steps: Optional[int] = None, env_offset: int = 0, **kwargs):
         from .spaces import Tuple
 
-        if kwargs.pop("render_mode", None) is not None:
-            raise TypeError(f"{id}: the device engine does not render (render_mode must be None)")
+        self._refuse_render_mode(id, kwargs)
         if kwargs:
             raise TypeError(f"{id} got an unexpected keyword argument {next(iter(kwargs))!r}")
         self.spec = ToyTextSpec(id, None, None)
         self.natural, self.sab = bool(natural), bool(sab)     # gym/envs/__init__.py:95-99 registers sab=True, natural=False
         super().__init__(num_envs, Tuple((Discrete(32), Discrete(11), Discrete(2))), Discrete(2))
-        entropy = int.from_bytes(os.urandom(8), "little")
-        self._handle = _native.Blackjack(num_envs, natural=natural, sab=sab, device=device, env_offset=env_offset,
-                                         max_episode_steps=-1 if max_episode_steps is None else int(max_episode_steps),
-                                         seed=entropy, action_seed=entropy ^ 0x9E3779B97F4A7C15)
         self._ctor = (device, env_offset, max_episode_steps)
-        self._actions = None
-        self._was_reset = False
+        self._handle = self._open_handle(*_seed_pair())
 
-    def __getstate__(self):
-        self._assert_is_running()
-        d = {k: v for k, v in self.__dict__.items() if k != "_handle"}
-        d["_snapshot"] = self._handle.snapshot()
-        return d
-
-    def __setstate__(self, d):
-        d = dict(d)
-        snap = d.pop("_snapshot")
-        self.__dict__.update(d)
+    def _open_handle(self, seed, action_seed):
         device, env_offset, limit = self._ctor
-        self._handle = _native.Blackjack(self.num_envs, natural=self.natural, sab=self.sab, device=device, env_offset=env_offset,
-                                         max_episode_steps=-1 if limit is None else int(limit),
-                                         seed=snap["base_seed"], action_seed=snap["action_seed"])
-        self._handle.restore(snap)
+        return _native.Blackjack(self.num_envs, natural=self.natural, sab=self.sab, device=device, env_offset=env_offset,
+                                 max_episode_steps=-1 if limit is None else int(limit), seed=seed, action_seed=action_seed)
 
     @staticmethod
     def _obs(cols):
         return (cols[0].copy(), cols[1].copy(), cols[2].copy())
 
-    def reset_wait(self, seed: Optional[Union[int, List[int]]] = None, options: Optional[dict] = None):
-        self._assert_is_running()
-        if seed is not None:
-            if isinstance(seed, (int, np.integer)):
-                if seed < 0:
-                    raise error.Error(f"Seed must be a non-negative integer or omitted, not {seed}")
-                self._handle.seed(int(seed), None, int(seed) ^ 0x9E3779B97F4A7C15)
-            else:
-                seeds = list(seed)
-                assert len(seeds) == self.num_envs
-                self._handle.seed(0, np.array(seeds, dtype=np.uint64), int(seeds[0]) ^ 0x9E3779B97F4A7C15)
-        cols = self._handle.reset_host()
-        self._was_reset = True
-        self._actions = None
-        return self._obs(cols), {}
+    def _seed_handle(self, base, per_env):
+        # the action stream follows the reset seed (sub-env 0's when every sub-env brings its own)
+        self._handle.seed(base, per_env, _seed_pair(base if per_env is None else int(per_env[0]))[1])
 
-    def step_async(self, actions):
-        self._assert_is_running()
-        if self._actions is not None:
-            raise error.AlreadyPendingCallError("Calling `step_async` while waiting for a pending call to `step` to "
-                                                "complete.", "step")
+    def _reset(self, options):
+        return self._obs(self._handle.reset_host()), {}
+
+    def _check_actions(self, actions):
         a = np.asarray(actions)
         if a.shape != (self.num_envs,) or not np.issubdtype(a.dtype, np.integer):
-            raise AssertionError(f"{actions!r} ({type(actions)}) invalid")
-        self._actions = np.ascontiguousarray(a, dtype=np.int64)
+            raise self._invalid_action(actions)
+        return np.ascontiguousarray(a, dtype=np.int64)
 
-    def step_wait(self):
-        self._assert_is_running()
-        if self._actions is None:
-            raise error.NoAsyncCallError("Calling `step_wait` without any prior call to `step_async`.", "step")
-        actions, self._actions = self._actions, None
-        if not self._was_reset:
-            raise error.ResetNeeded("Cannot call env.step() before calling env.reset()")
-        try:
-            cols, rew, term, trunc, fin = self._handle.step_host(actions, pooled=True)
-        except _native.MxvError as e:
-            if e.code == _native.ERR_INVALID_ACTION:
-                raise AssertionError(f"{actions!r} ({type(actions)}) invalid") from None   # blackjack.py:122
-            raise
+    def _step(self, actions):
+        cols, rew, term, trunc, fin = self._handle.step_host(actions, pooled=True)   # an action outside {0, 1}: blackjack.py:122 asserts
         n = self.num_envs
         done = term | trunc
         infos = LazyInfos()
         if done.any():
             idx = np.flatnonzero(done)
-
-            def build_final_obs():
-                arr = np.full(n, None, dtype=object)
-                for i in idx:
-                    arr[i] = (int(fin[0, i]), int(fin[1, i]), bool(fin[2, i]))   # _get_obs(): (int, int, bool)
-                return arr
-
-            def build_final_info():
-                arr = np.full(n, None, dtype=object)
-                for i in idx:
-                    arr[i] = {}
-                return arr
-
-            dict.__setitem__(infos, "final_observation", _Pending(build_final_obs))
-            dict.__setitem__(infos, "_final_observation", done.copy())
-            dict.__setitem__(infos, "final_info", _Pending(build_final_info))
-            dict.__setitem__(infos, "_final_info", done.copy())
+            _set_final_infos(infos, done,     # _get_obs(): (int, int, bool)
+                             _Pending(lambda: _object_array(n, idx, lambda i: (int(fin[0, i]), int(fin[1, i]), bool(fin[2, i])))),
+                             _Pending(lambda: _object_array(n, idx, lambda i: {})))
         return self._obs(cols), rew, term, trunc, infos
-
-    def close_extras(self, **kwargs):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            h.close()
-
-    def _assert_is_running(self):
-        if self.closed:
-            raise error.ClosedEnvironmentError(f"Trying to operate on `{type(self).__name__}`, after a call to `close()`.")
-
-    @property
-    def unwrapped(self):
-        return self
-
-    @property
-    def handle(self) -> "_native.Blackjack":
-        return self._handle

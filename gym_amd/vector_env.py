@@ -254,7 +254,135 @@ class VectorEnvWrapper(VectorEnv):
             env.__del__()
 
 
-class HipVectorEnv(VectorEnv):
+def _seed_pair(seed: Optional[int] = None):
+    """(seed, action seed) of an engine handle; seed=None: fresh OS entropy, as Env.reset(seed=None) draws it (seeding.py:24)."""
+    if seed is None:
+        seed = int.from_bytes(os.urandom(8), "little")
+    return seed, seed ^ 0x9E3779B97F4A7C15
+
+
+def _object_array(n: int, idx, item) -> np.ndarray:
+    """VectorEnv._add_info's object array (vector_env.py:208-258): length n, item(i) at every i of idx, None elsewhere."""
+    arr = np.full(n, None, dtype=object)
+    for i in idx:
+        arr[i] = item(i)
+    return arr
+
+
+def _set_final_infos(infos: LazyInfos, done: np.ndarray, final_obs, final_info):
+    """The four keys of a step in which sub-envs finished (sync_vector_env.py:152-169).  `final_obs` / `final_info`: the array, or a
+    _Pending that builds it on first access; `done` must be the caller's own array (it becomes `_final_observation`)."""
+    dict.__setitem__(infos, "final_observation", final_obs)
+    dict.__setitem__(infos, "_final_observation", done)
+    dict.__setitem__(infos, "final_info", final_info)
+    dict.__setitem__(infos, "_final_info", _Pending(done.copy))   # its own array, like the reference's (made on access)
+
+
+class _EngineVectorEnv(VectorEnv):
+    """What the NumPy adapters of the three engines share (HipVectorEnv, toy_text.HipTabularVectorEnv / HipBlackjackVectorEnv): seeding,
+    the step_async / step_wait protocol and its errors, closing and pickling around one `_native` handle in `self._handle`.  A family
+    supplies _open_handle(), _reset(), _check_actions() and _step(), and keeps whatever else is its own."""
+
+    metadata = {"render_modes": []}
+    render_mode = None
+    _actions = None         # what step_async() checked and step_wait() will play
+    _was_reset = False
+    _transient = ()         # attributes besides the handle that stay out of a pickle
+
+    @staticmethod
+    def _refuse_render_mode(id: str, kwargs: dict):
+        if kwargs.pop("render_mode", None) is not None:
+            raise TypeError(f"{id}: the device engine does not render (render_mode must be None)")
+
+    # -- reset ---------------------------------------------------------------------------------------
+    def reset_wait(self, seed: Optional[Union[int, List[int]]] = None, options: Optional[dict] = None):
+        """sync_vector_env.py:90-129."""
+        self._assert_is_running()
+        options = self._reset_options(options)
+        if seed is not None:
+            one = isinstance(seed, (int, np.integer))
+            seeds = [seed] if one else list(seed)
+            assert one or len(seeds) == self.num_envs
+            for s in seeds:
+                if not (isinstance(s, (int, np.integer)) and s >= 0):
+                    raise error.Error(f"Seed must be a non-negative integer or omitted, not {s}")
+            if one:
+                self._seed_handle(int(seed), None)   # env i gets seed + i (sync_vector_env.py:106-107)
+            else:
+                self._seed_handle(0, np.array(seeds, dtype=np.uint64))
+        out = self._reset(options)
+        self._was_reset = True
+        self._actions = None
+        return out
+
+    def _reset_options(self, options):
+        """Checks `options` (before the seed is looked at) and returns what _reset() needs of them."""
+        return None
+
+    def _seed_handle(self, base: int, per_env):
+        self._handle.seed(base, per_env)
+
+    # -- step ----------------------------------------------------------------------------------------
+    def step_async(self, actions):
+        """sync_vector_env.py:131-133."""
+        self._assert_is_running()
+        if self._actions is not None:
+            raise error.AlreadyPendingCallError("Calling `step_async` while waiting for a pending call to `step` to "
+                                                "complete.", "step")
+        self._actions = self._check_actions(actions)
+
+    def step_wait(self):
+        """sync_vector_env.py:135-169."""
+        self._assert_is_running()
+        if self._actions is None:
+            raise error.NoAsyncCallError("Calling `step_wait` without any prior call to `step_async`.", "step")
+        actions, self._actions = self._actions, None
+        if not self._was_reset:
+            raise error.ResetNeeded("Cannot call env.step() before calling env.reset()")
+        try:
+            return self._step(actions)
+        except _native.MxvError as e:
+            if e.code == _native.ERR_INVALID_ACTION:
+                raise self._invalid_action(actions) from None
+            if e.code == _native.ERR_RESET_NEEDED:
+                raise error.ResetNeeded("Cannot call env.step() before calling env.reset()") from None
+            raise
+
+    def _invalid_action(self, actions) -> Exception:
+        """What the reference raises for an action outside the space: Discrete.contains fails its assert (discrete.py:83-94)."""
+        return AssertionError(f"{actions!r} ({type(actions)}) invalid")
+
+    # -- misc ----------------------------------------------------------------------------------------
+    def close_extras(self, **kwargs):
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            h.close()
+
+    def _assert_is_running(self):
+        if self.closed:
+            raise error.ClosedEnvironmentError(f"Trying to operate on `{type(self).__name__}`, after a call to `close()`.")
+
+    @property
+    def handle(self):
+        """The engine handle (device-pointer API: see gym_amd.rollout.DeviceRollout)."""
+        return self._handle
+
+    # -- pickling: how the reference's envs are checkpointed (tests/envs/test_envs.py:192-200) ----------------------
+    def __getstate__(self):
+        self._assert_is_running()
+        d = {k: v for k, v in self.__dict__.items() if k != "_handle" and k not in self._transient}
+        d["_snapshot"] = self._handle.snapshot()
+        return d
+
+    def __setstate__(self, d):
+        d = dict(d)
+        snap = d.pop("_snapshot")
+        self.__dict__.update(d)
+        self._handle = self._open_handle(snap["base_seed"], snap["action_seed"])
+        self._handle.restore(snap)
+
+
+class HipVectorEnv(_EngineVectorEnv):
     """`num_envs` copies of one classic-control env, resident on one MI355X.
 
     Same call surface and return contract as SyncVectorEnv: observations float32 (N, O) (a fresh array
@@ -265,8 +393,7 @@ class HipVectorEnv(VectorEnv):
     PCG64, so seeded initial states differ from the reference's (RNG).
     """
 
-    metadata = {"render_modes": []}
-    render_mode = None
+    _transient = ("_views", "_copy_pool")
 
     def __init__(self, id: str, num_envs: int = 1, *, device: int = 0, max_episode_steps: Optional[int] = None,
                  env_offset: int = 0, copy: bool = True, zero_copy: bool = False, autoreset: bool = True, **kwargs):
@@ -288,7 +415,6 @@ class HipVectorEnv(VectorEnv):
         limit = self.spec.max_episode_steps if max_episode_steps is None else max_episode_steps
         self._max_episode_steps = -1 if limit is None else int(limit)
         self._discrete = isinstance(action_space, Discrete)
-        entropy = int.from_bytes(os.urandom(8), "little")  # Env.reset(seed=None) = fresh OS entropy (seeding.py:24)
         render_mode = kwargs.pop("render_mode", None)
         from . import _render
 
@@ -299,13 +425,8 @@ class HipVectorEnv(VectorEnv):
         # autoreset=False (MXV_FLAG_NO_AUTORESET): dynamics + TimeLimit only, a finished env stays finished until reset() — the single-env
         # contract of gym.Env (gym/core.py:75-184), which gym_amd.single_env.HipEnv builds on
         self.autoreset = bool(autoreset)
-        self._handle = _native.Handle(self.kind, num_envs, self._max_episode_steps, device=device,
-                                      env_offset=env_offset, seed=entropy, action_seed=entropy ^ 0x9E3779B97F4A7C15,
-                                      **({} if autoreset else {"flags": _native.FLAG_NO_AUTORESET}))
-        if self._arrow_image is not None:
-            _render.attach_image(self._handle, self._arrow_image)
-        self._actions = None
-        self._was_reset = False
+        self._device, self._env_offset = device, env_offset
+        self._handle = self._open_handle(*_seed_pair())
         self._per_env = False  # True while sub-envs hold differing physics attributes (set_attr with a list)
         # large envs: info["final_observation"] rows arrive packed (indices + rows of the finished envs), never as a dense array
         self._packed = bool(getattr(self._handle, "final_packed", lambda on: False)(True))
@@ -449,7 +570,7 @@ class HipVectorEnv(VectorEnv):
         self._per_env = True
 
     # -- reset ---------------------------------------------------------------------------------------
-    def _reset_bounds(self, options: Optional[dict]):
+    def _reset_options(self, options: Optional[dict]):
         if options is None:
             return None
         if self.kind == PENDULUM:  # pendulum.py:141-152
@@ -464,31 +585,12 @@ class HipVectorEnv(VectorEnv):
             raise ValueError(f"Lower bound ({low}) must be lower than higher bound ({high}).")
         return np.array([low, high], dtype=np.float64)
 
-    def reset_wait(self, seed: Optional[Union[int, List[int]]] = None, options: Optional[dict] = None):
-        """sync_vector_env.py:90-129."""
-        self._assert_is_running()
-        bounds = self._reset_bounds(options)
-        if seed is not None:
-            if isinstance(seed, (int, np.integer)):
-                if seed < 0:
-                    raise error.Error(f"Seed must be a non-negative integer or omitted, not {seed}")
-                self._handle.seed(int(seed) + 0, None)  # env i gets seed + i (sync_vector_env.py:106-107)
-            else:
-                seeds = list(seed)
-                assert len(seeds) == self.num_envs
-                for s in seeds:
-                    if not (isinstance(s, (int, np.integer)) and s >= 0):
-                        raise error.Error(f"Seed must be a non-negative integer or omitted, not {s}")
-                self._handle.seed(0, np.array(seeds, dtype=np.uint64))
+    def _reset(self, bounds):
         if self._own_arrays:
-            obs = self._handle.reset_host(bounds=bounds)
-        else:
-            io = self._io()   # creates the mapped block on first use
-            self._handle.reset_mapped(bounds=bounds)
-            obs = io["obs"]
-        self._was_reset = True
-        self._actions = None
-        return obs, {}
+            return self._handle.reset_host(bounds=bounds), {}
+        io = self._io()   # creates the mapped block on first use
+        self._handle.reset_mapped(bounds=bounds)
+        return io["obs"], {}
 
     def _io(self):
         if self._views is None:
@@ -496,55 +598,34 @@ class HipVectorEnv(VectorEnv):
         return self._views
 
     # -- step ----------------------------------------------------------------------------------------
-    def step_async(self, actions):
-        """sync_vector_env.py:131-133."""
-        self._assert_is_running()
-        if self._actions is not None:
-            raise error.AlreadyPendingCallError("Calling `step_async` while waiting for a pending call to `step` to "
-                                                "complete.", "step")
+    def _check_actions(self, actions):
         n = self.num_envs
         a = np.asarray(actions)
         if self._discrete:
             if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
-                # Discrete.contains (discrete.py:83-94) accepts integers only: the reference asserts
-                raise AssertionError(f"{actions!r} ({type(actions)}) invalid")
-            self._actions = np.ascontiguousarray(a, dtype=self._handle.action_dtype)
-        else:
-            if a.size != n:
-                raise AssertionError(f"expected {n} actions of shape (1,), got array of shape {a.shape}")
-            self._actions = np.ascontiguousarray(a, dtype=np.float32).reshape(n)
+                raise self._invalid_action(actions)     # Discrete.contains accepts integers only
+            return np.ascontiguousarray(a, dtype=self._handle.action_dtype)
+        if a.size != n:
+            raise AssertionError(f"expected {n} actions of shape (1,), got array of shape {a.shape}")
+        return np.ascontiguousarray(a, dtype=np.float32).reshape(n)
 
-    def step_wait(self):
-        """sync_vector_env.py:135-169."""
-        self._assert_is_running()
-        if self._actions is None:
-            raise error.NoAsyncCallError("Calling `step_wait` without any prior call to `step_async`.", "step")
-        actions, self._actions = self._actions, None
-        if not self._was_reset:
-            raise error.ResetNeeded("Cannot call env.step() before calling env.reset()")
-        try:
-            if self._own_arrays:
-                obs, rew, term, trunc, fin = self._handle.step_host_block(actions, want_final=True)
-            else:
-                io = self._io()
-                io["actions"][:] = actions
-                self._handle.step_mapped()
-                obs, fin = io["obs"], io["final_obs"]
-                rew, term, trunc = io["reward"], io["terminated"], io["truncated"]
-                if not self.zero_copy:      # fresh-to-the-caller copies out of a recycling pool (no page faults per step)
-                    pool = self.__dict__.setdefault("_copy_pool", _native._ArrayPool())
-                    outs = []
-                    for src in (rew, term, trunc):
-                        dst = pool.take(src.shape, src.dtype)
-                        np.copyto(dst, src)
-                        outs.append(dst)
-                    rew, term, trunc = outs
-        except _native.MxvError as e:
-            if e.code == _native.ERR_INVALID_ACTION:
-                raise AssertionError(f"{actions!r} ({type(actions)}) invalid") from None
-            if e.code == _native.ERR_RESET_NEEDED:
-                raise error.ResetNeeded("Cannot call env.step() before calling env.reset()") from None
-            raise
+    def _step(self, actions):
+        if self._own_arrays:
+            obs, rew, term, trunc, fin = self._handle.step_host_block(actions, want_final=True)
+        else:
+            io = self._io()
+            io["actions"][:] = actions
+            self._handle.step_mapped()
+            obs, fin = io["obs"], io["final_obs"]
+            rew, term, trunc = io["reward"], io["terminated"], io["truncated"]
+            if not self.zero_copy:      # fresh-to-the-caller copies out of a recycling pool (no page faults per step)
+                pool = self.__dict__.setdefault("_copy_pool", _native._ArrayPool())
+                outs = []
+                for src in (rew, term, trunc):
+                    dst = pool.take(src.shape, src.dtype)
+                    np.copyto(dst, src)
+                    outs.append(dst)
+                rew, term, trunc = outs
         infos = LazyInfos()
         done = term | trunc
         if done.any():
@@ -569,69 +650,34 @@ class HipVectorEnv(VectorEnv):
 
             def build_final_obs():
                 idx, rows = finished()
-                arr = np.full(n, None, dtype=object)
-                for j, i in enumerate(idx):
-                    arr[i] = rows[j]
-                return arr
+                row = iter(rows)            # the rows come in the order of idx
+                return _object_array(n, idx, lambda i: next(row))
 
             def build_final_info():
-                idx, _ = finished()
-                arr = np.full(n, None, dtype=object)
-                for i in idx:
-                    arr[i] = {}
-                return arr
+                return _object_array(n, finished()[0], lambda i: {})
 
-            dict.__setitem__(infos, "final_observation", _Pending(build_final_obs))
-            dict.__setitem__(infos, "_final_observation", done)
-            dict.__setitem__(infos, "final_info", _Pending(build_final_info))
-            dict.__setitem__(infos, "_final_info", _Pending(done.copy))   # its own array, like the reference's (made on access)
+            _set_final_infos(infos, done, _Pending(build_final_obs), _Pending(build_final_info))
         return obs, rew, term, trunc, infos
 
     # -- misc ----------------------------------------------------------------------------------------
     def close_extras(self, **kwargs):
-        h = getattr(self, "_handle", None)
         self._views = None   # arrays the caller still holds keep the pinned block (and with it the handle) alive
-        if h is not None:
-            h.close()
+        super().close_extras(**kwargs)
 
-    def _assert_is_running(self):
-        if self.closed:
-            raise error.ClosedEnvironmentError(f"Trying to operate on `{type(self).__name__}`, after a call to `close()`.")
-
-    @property
-    def unwrapped(self):
-        """gym.Env surface used by gym.make (`env.unwrapped.spec = ...`, gym/envs/registration.py:656)."""
-        return self
-
-    # -- pickling: how the reference's envs are checkpointed (tests/envs/test_envs.py:192-200) ----------------------
-    def __getstate__(self):
-        self._assert_is_running()
-        d = {k: v for k, v in self.__dict__.items() if k not in ("_handle", "_views", "_copy_pool")}
-        d["_snapshot"] = self._handle.snapshot()
-        d["_device"] = self._handle.device
-        return d
-
-    def __setstate__(self, d):
-        d = dict(d)
-        snap, device = d.pop("_snapshot"), d.pop("_device")
-        self.__dict__.update(d)
-        self._views = None
-        self._handle = _native.Handle(snap["env_id"], snap["num_envs"], snap["max_episode_steps"], device=device,
-                                      env_offset=snap["env_offset"], seed=snap["base_seed"], action_seed=snap["action_seed"],
-                                      flags=snap["flags"])
-        if self.__dict__.get("_arrow_image") is not None:   # Pendulum frames: the image travels in the pickle, last_u in the snapshot
+    def _open_handle(self, seed, action_seed):
+        h = _native.Handle(self.kind, self.num_envs, self._max_episode_steps, device=self._device, env_offset=self._env_offset,
+                           seed=seed, action_seed=action_seed, **({} if self.autoreset else {"flags": _native.FLAG_NO_AUTORESET}))
+        if self._arrow_image is not None:   # Pendulum frames (in a pickle the image travels in __dict__, last_u in the snapshot)
             from . import _render
 
-            _render.attach_image(self._handle, self._arrow_image)
-        self._handle.restore(snap)
+            _render.attach_image(h, self._arrow_image)
+        return h
+
+    def __setstate__(self, d):
+        super().__setstate__(d)
+        self._views = None
         self._packed = bool(self._handle.final_packed(True))
         self._own_arrays = self.copy or self._packed
-
-    # -- escape hatch for device-resident use ----------------------------------------------------------
-    @property
-    def handle(self) -> "_native.Handle":
-        """The engine handle (device-pointer API: see gym_amd.rollout.DeviceRollout)."""
-        return self._handle
 
 
 def _sub_env_wrappers(wrappers):

@@ -101,8 +101,9 @@ def test_rollout_results_do_not_depend_on_where_the_trajectory_tensors_live(layo
 def test_default_trajectory_buffers_sort_large_sets_and_leave_small_ones_alone():
     r = DeviceRollout("CartPole-v1", 1 << 18, seed=0, action_seed=1)
     r.reset(seed=0)
+    assert r.last_placement is None                    # there from construction on, None until a sorted / placed allocation
     small = r.trajectory_buffers(16)
-    assert not hasattr(r, "last_placement")
+    assert r.last_placement is None
     big = r.rollout_per_step(256)                      # out=None: what a user gets
     assert r.last_placement["kind"] == "sorted" and big["obs"].shape == (256, 1 << 18, 4)
     del small, big
@@ -118,6 +119,7 @@ def test_tabular_rollout_sorts_its_four_streams_two_and_two():
     b = TabularRollout("FrozenLake-v1", n, seed=2, action_seed=3)
     a.reset(seed=2)
     b.reset(seed=2)
+    assert a.last_placement is None
     ta = a.trajectory_buffers(k)
     assert a.last_placement["kind"] == "sorted" and "balanced" in a.last_placement
     tb = b.trajectory_buffers(k, layout="separate")
