@@ -22,6 +22,10 @@
 // Numerics: sums are exact-order fp64 (no atomics), so results are bit-reproducible; they differ from the reference only
 // by the float32 accumulation error the reference's own np.mean/np.var carry (the test suite's CPU restatement has both
 // arithmetics: the reference's, pinned bit-exact by goldens generated from the live wrappers, and this definition).
+// The ORDER of the additions below is restated in NumPy by tests/norm_tree_host.py: tests/test_gpu_norm_trees.py holds the three sums
+// kernels to it bit for bit (and to int64 sums of integers, and to exact sums under the bound of the tree's depth), and
+// tests/test_gpu_norm_scan.py holds scan_kernel and the apply kernels to the suite's CPU restatement bit for bit on synthetic sums (every
+// chunk of kScanChunk steps, 1..kMaxWorld ranks).  Change an order here and the twin there changes with it.
 // Built with -ffp-contract=off like the rest of the engine: explicit __fma_rn only where the product is exact anyway.
 #include <hip/hip_runtime.h>
 
