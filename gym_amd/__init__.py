@@ -28,6 +28,8 @@ _LAZY = {
     "TabularRollout": ("gym_amd.toy_text", "TabularRollout"),
     "HipBlackjackVectorEnv": ("gym_amd.toy_text", "HipBlackjackVectorEnv"),
     "BlackjackRollout": ("gym_amd.toy_text", "BlackjackRollout"),
+    "gae": ("gym_amd.returns", "gae"),
+    "discounted_returns": ("gym_amd.returns", "discounted_returns"),
 }
 
 

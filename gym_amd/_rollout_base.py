@@ -51,6 +51,31 @@ class _RolloutBase:
         engine's stream (no host synchronisation).  Use before touching output tensors outside `with torch.cuda.stream(r.stream)`."""
         self._torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
+    def advantages(self, traj, values, last_value=None, *, gamma: float = 0.99, lam: float = 0.95, final_values=None, out=None):
+        """GAE(lambda) over the chunk in `traj` (the dict of rollout_per_step / rollout_tape) -> (advantages, returns), float32 [K, N]:
+        gym_amd.returns.gae on traj["reward"], traj["terminated"], traj["truncated"], launched on the caller's current stream after
+        ready(), so that it waits for the rollout on the GPU.
+
+        `values` [K, N]: the learner's V of the observation the action of step t was taken FROM.  That is NOT V(traj["obs"]):
+        traj["obs"][t] is the observation AFTER step t, and after an autoreset the next episode's first one.  With `first_obs` the
+        observation the chunk started from (reset()'s, or traj["obs"][K-1] of the previous chunk),
+            values = V(gym_amd.returns.pre_step_observations(first_obs, traj["obs"]))    # cat(first_obs[None], traj["obs"][:-1])
+            last_value = V(traj["obs"][K-1])                                             # [N]
+        `final_values` [K, N]: V(traj["final_obs"]) (trajectory_buffers(want_final=True)), which a truncated step bootstraps from."""
+        from .returns import gae
+
+        self.ready()
+        return gae(traj["reward"], traj["terminated"], traj["truncated"], values, last_value, gamma=gamma, lam=lam,
+                   final_values=final_values, out=out)
+
+    def returns_to_go(self, traj, *, gamma: float = 0.99, last_value=None, final_values=None, out=None):
+        """Discounted returns-to-go of the chunk in `traj` -> float32 [K, N]: gym_amd.returns.discounted_returns after ready()."""
+        from .returns import discounted_returns
+
+        self.ready()
+        return discounted_returns(traj["reward"], traj["terminated"], traj["truncated"], gamma=gamma, last_value=last_value,
+                                  final_values=final_values, out=out)
+
     def synchronize(self):
         """Wait for the engine's stream; raises if a step saw an out-of-range action."""
         try:
