@@ -39,7 +39,7 @@ COMM_ID_BYTES = 128
 EXPORTS = (
     "mxv_env_dims", "mxv_default_params", "mxv_default_reset_bounds", "mxv_version", "mxv_create", "mxv_destroy",
     "mxv_last_error", "mxv_seed", "mxv_seed_actions", "mxv_reset", "mxv_step", "mxv_step_sampled", "mxv_rollout",
-    "mxv_rollout_tape", "mxv_sample_actions", "mxv_last_launch", "mxv_reset_host", "mxv_step_host", "mxv_get_state", "mxv_set_state", "mxv_get_counters",
+    "mxv_rollout_tape", "mxv_sample_actions", "mxv_last_launch", "mxv_last_launch_snapshot", "mxv_reset_host", "mxv_step_host", "mxv_get_state", "mxv_set_state", "mxv_get_counters",
     "mxv_set_counters", "mxv_set_device_clock", "mxv_set_obs_partials", "mxv_set_return_partials", "mxv_obs_partials_layout", "mxv_get_episodes", "mxv_set_episodes", "mxv_get_params", "mxv_set_params", "mxv_set_params_per_env", "mxv_get_params_per_env", "mxv_episode_stats", "mxv_set_episode_outputs", "mxv_episode_stats_host", "mxv_set_running_returns", "mxv_sync", "mxv_get_stream", "mxv_set_stream",
     "mxv_rollout_mixed", "mxv_set_final_snapshot", "mxv_comm_unique_id", "mxv_comm_init", "mxv_comm_destroy", "mxv_allgather_outputs", "mxv_allgather_wait", "mxv_comm_stream",
     "mxv_host_io", "mxv_step_mapped", "mxv_reset_mapped", "mxv_final_packed", "mxv_final_packed_view", "mxv_final_packed_stats_view", "mxv_write_probe", "mxv_write_probe_env", "mxv_host_alloc", "mxv_host_free",
@@ -194,6 +194,7 @@ def _load():
         "mxv_rollout_tape": ([vp, i32, i32, vp, vp, vp, vp, vp, vp], C.c_int),
         "mxv_sample_actions": ([vp, vp], C.c_int),
         "mxv_last_launch": ([vp, C.POINTER(MxvLaunchInfo)], C.c_int),
+        "mxv_last_launch_snapshot": ([vp, C.POINTER(i32), C.POINTER(i32)], C.c_int),
         "mxv_reset_host": ([vp, vp, vp, vp], C.c_int),
         "mxv_step_host": ([vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "mxv_get_state": ([vp, vp, vp], C.c_int),
@@ -774,7 +775,19 @@ class Handle(_Engine):
         """Which kernel instantiation the last step / rollout launch took (mxv_last_launch)."""
         info = MxvLaunchInfo()
         self._check(lib.mxv_last_launch(self._h, C.byref(info)))
-        return {k: int(getattr(info, k)) for k, _ in MxvLaunchInfo._fields_}
+        out = {k: int(getattr(info, k)) for k, _ in MxvLaunchInfo._fields_}
+        out["snapshot"] = int(self._final_snapshot()[1])     # that launch was handed the final snapshot's buffers (mxv_last_launch_snapshot)
+        return out
+
+    def _final_snapshot(self):
+        attached, deposited = C.c_int32(), C.c_int32()
+        self._check(lib.mxv_last_launch_snapshot(self._h, C.byref(attached), C.byref(deposited)))
+        return bool(attached.value), bool(deposited.value)
+
+    @property
+    def final_snapshot_attached(self) -> bool:
+        """Whether the handle holds final-snapshot buffers now (mxv_set_final_snapshot), read from the handle itself."""
+        return self._final_snapshot()[0]
 
     def set_counters(self, t: int, r: int):
         self._check(lib.mxv_set_counters(self._h, int(t), int(r)))

@@ -84,6 +84,7 @@ struct mxv_handle : mxv::HostCore {
     bool state_injected = false;  // set by mxv_set_state / unusual reset bounds, consumed by the next step launch
     bool state_out_of_range = false;  // Pendulum only: an injected angle beyond the unguarded range stays until a full reset
     LaunchInfo last_launch{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // mxv_last_launch
+    bool last_launch_snapshot = false;  // the last launch was handed the final snapshot's pointers (mxv_last_launch_snapshot)
     bool step_noise = false;      // Acrobot torque_noise_max > 0 (acrobot.py:202-205): the step draws from the step-noise stream
     EnvParams P{};
     bool default_params = true;
@@ -159,7 +160,8 @@ int check_latched(mxv_handle *h) {
 }
 
 // Host steps of a small env (the kernel reads and writes the pinned I/O block over PCIe): the error word lives in that block too,
-// so the call is one launch and one synchronisation — no 4-byte copy to fetch a device-side latch (a quarter of the 17 us).
+// so the call is one launch and one synchronisation — no 4-byte copy to fetch a device-side latch (a quarter of the 17 us).  (The
+// handle's own latch lives in pinned host memory as well by now — alloc_latch, mxv_host.hpp — and is read the same way.)
 struct ErrInBlock {
     mxv_handle *h;
     explicit ErrInBlock(mxv_handle *hh) : h(hh) { h->err_in_block = h->hostmap; }
@@ -345,6 +347,7 @@ int do_step(mxv_handle *h, const void *actions, void *actions_out, float *obs, v
     } else {
         MXV_HIP(h, launch_step(h->cfg.env_id, h->param_mode(), a, h->stream, &h->last_launch));
     }
+    h->last_launch_snapshot = false;   // only the K-step calls deposit a snapshot
     h->state_injected = false;
     if (int rc = track_step(h, track)) return rc;
     if (self_clock) {
@@ -622,13 +625,12 @@ int mxv_create(const mxv_config *cfg, mxv_handle **out) {
     MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->episodes, n * sizeof(uint32_t)));
     MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->t_dev, sizeof(uint64_t)));
     MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->clock_ticket, sizeof(uint32_t)));
-    MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->err, sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_destroy, alloc_latch(h));
     MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->state, 0, n * h->S * sizeof(double), h->stream));
     MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->elapsed, 0, n * sizeof(int32_t), h->stream));
     MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->episodes, 0, n * sizeof(uint32_t), h->stream));
     MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->t_dev, 0, sizeof(uint64_t), h->stream));
     MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->clock_ticket, 0, sizeof(uint32_t), h->stream));
-    MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
     if (cfg->env_id == MXV_CARTPOLE && (cfg->flags & MXV_FLAG_NO_AUTORESET)) {   // steps_beyond_terminated marks (cartpole.py:169-184)
         MXV_CREATE_HIP(h, mxv_destroy, hipMalloc((void **)&h->beyond, n));
         MXV_CREATE_HIP(h, mxv_destroy, hipMemsetAsync(h->beyond, 0, n, h->stream));
@@ -755,6 +757,7 @@ int fused_launch(mxv_handle *h, int32_t K, int32_t per_step, const void *actions
     const float *track = nullptr;
     if (int rc = track_source(h, actions_tape, K - 1, K, &track)) return rc;
     MXV_HIP(h, launch_step(h->cfg.env_id, h->param_mode(), a, h->stream, &h->last_launch));
+    h->last_launch_snapshot = a.snap_obs != nullptr;
     h->state_injected = false;
     if (int rc = track_step(h, track)) return rc;
     if (int rc = clock_add(h, K)) return rc;
@@ -835,6 +838,7 @@ int mxv_rollout(mxv_handle *h, int32_t K, int32_t per_step, int32_t mode, void *
         if (!h->dev_clock) MXV_HIP(h, launch_set_word(h->t_dev, h->t, h->stream));
         MXV_HIP(h, hipGraphLaunch(it->second, h->stream));
     }
+    h->last_launch_snapshot = false;   // single-step launches: the snapshot, if any, is copied below
     h->state_injected = false;
     if (int rc = track_step(h, track)) return rc;
     if (int rc = clock_add(h, K)) return rc;
@@ -1070,13 +1074,8 @@ int mapped_finish(mxv_handle *h, bool stepped) {
             if (int rc = fetch_final_rows(h, h->fin_packed ? nullptr : fin_pinned)) return rc;
         }
     }
-    if (!h->hostmap) {  // (a small env's kernel raised the word in the pinned block itself: see ErrInBlock)
-        MXV_HIP(h, hipMemcpyAsync(h->hm_err, h->err, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-        if (*h->hm_err != 0) MXV_HIP(h, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
-    } else {
-        MXV_HIP(h, hipStreamSynchronize(h->stream));
-    }
+    MXV_HIP(h, hipStreamSynchronize(h->stream));
+    if (!h->hostmap) *h->hm_err = take_latched_drained(h);  // (a small env's kernel raised the word in the pinned block itself: see ErrInBlock)
     const int rc = take_block_error(h);
     if (rc != MXV_OK && stepped) (void)clock_add(h, -1);  // the reference raises before stepping anything further
     return rc;
@@ -1211,6 +1210,14 @@ int mxv_last_launch(mxv_handle *h, mxv_launch_info *out) {
     if (!out) return fail(h, MXV_ERR_INVALID_ARG, "mxv_last_launch: out is NULL");
     static_assert(sizeof(mxv_launch_info) == sizeof(LaunchInfo), "mxv_launch_info mirrors LaunchInfo member for member");
     std::memcpy(out, &h->last_launch, sizeof(*out));
+    return MXV_OK;
+}
+
+int mxv_last_launch_snapshot(mxv_handle *h, int32_t *attached, int32_t *deposited) {
+    MXV_CHECK(h);
+    if (!attached && !deposited) return fail(h, MXV_ERR_INVALID_ARG, "mxv_last_launch_snapshot: both outputs are NULL");
+    if (attached) *attached = h->snap_obs != nullptr ? 1 : 0;
+    if (deposited) *deposited = h->last_launch_snapshot ? 1 : 0;
     return MXV_OK;
 }
 
@@ -1759,7 +1766,7 @@ int render_view(mxv_handle *h, RenderView *v) {
     v->state = h->state;
     v->params_pe = h->params_pe;
     std::memcpy(v->P, h->P.p, sizeof v->P);
-    v->err = h->err;
+    v->err = h->err + kRenderLatchWord;   // the render kernels' own word of the latch block (a plain store, no atomic on host memory)
     v->last_u = h->last_u;
     v->sat = h->blit_sat;
     v->img_h = h->blit_h;

@@ -467,11 +467,10 @@ int mxv_bj_create(const mxv_bj_config *cfg, mxv_bj **out) {
     h->own_stream = err == hipSuccess;
     if (err == hipSuccess) err = hipMalloc((void **)&h->state, n * 4);
     if (err == hipSuccess) err = hipMalloc((void **)&h->elapsed, n * 4);
-    if (err == hipSuccess) err = hipMalloc((void **)&h->err, 4);
+    if (err == hipSuccess) err = alloc_latch(h);
     if (err == hipSuccess) err = hipMalloc((void **)&h->t_dev, 8);
     if (err == hipSuccess) err = hipMemsetAsync(h->state, 0, n * 4, h->stream);
     if (err == hipSuccess) err = hipMemsetAsync(h->elapsed, 0, n * 4, h->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(h->err, 0, 4, h->stream);
     if (err == hipSuccess) err = hipMemsetAsync(h->t_dev, 0, 8, h->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(h->stream);
     if (err != hipSuccess) {

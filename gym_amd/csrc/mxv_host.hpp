@@ -86,7 +86,11 @@ struct HostCore {
     int64_t num_envs = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    int32_t *err = nullptr;          // latched kernel error word
+    // Latched kernel error words: one block of pinned, coherent, device-mapped host memory (alloc_latch).  The kernels raise their
+    // single-bit codes in it with plain stores; the host reads and clears it after a stream synchronisation — no copy command follows a
+    // launch.  err[0]: the step / rollout kernels; err[kRenderLatchWord]: the render kernels (a plain store each, the host ORs them).
+    int32_t *err = nullptr;          // the block as the kernels address it (stable for the handle's life: recorded hipGraphs keep it)
+    volatile int32_t *err_host = nullptr;   // the same block as the host reads it
     std::string error;
     uint64_t t = 0;                  // vector steps taken (the action / step stream position)
     uint32_t r = 0;                  // explicit resets
@@ -100,6 +104,22 @@ struct HostCore {
     float *ep_acc = nullptr, *st_ep_r = nullptr, *ep_return_out = nullptr;
     int32_t *st_ep_l = nullptr, *ep_length_out = nullptr;
 };
+
+constexpr int kLatchWords = 2, kRenderLatchWord = 1;
+// the block is padded to one 64-byte line of its own: nothing else of the host shares the line the kernels store into over the bus
+constexpr size_t kLatchBytes = 64;
+static_assert(kLatchWords * sizeof(int32_t) <= kLatchBytes, "the latch words fit their line");
+
+inline hipError_t alloc_latch(HostCore *h) {
+    void *host = nullptr, *dev = nullptr;
+    hipError_t e = hipHostMalloc(&host, kLatchBytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) return e;
+    h->err_host = (volatile int32_t *)host;
+    for (int i = 0; i < kLatchWords; ++i) h->err_host[i] = 0;
+    e = hipHostGetDevicePointer(&dev, host, 0);
+    if (e == hipSuccess) h->err = (int32_t *)dev;
+    return e;
+}
 
 inline int use_device(HostCore *h) {
     MXV_HIP(h, hipSetDevice(h->device));
@@ -150,13 +170,23 @@ inline int set_device_clock(HostCore *h, int32_t on) {
     return MXV_OK;
 }
 
-// The latched error word, read back (synchronises the stream) and cleared: *word = 0 when nothing was latched.  What a raised bit means is
+// The latched error words once the stream has drained: their OR, cleared (0 when nothing was latched).
+inline int32_t take_latched_drained(HostCore *h) {
+    int32_t word = 0;
+    for (int i = 0; i < kLatchWords; ++i) {
+        const int32_t w = h->err_host[i];
+        if (w != 0) h->err_host[i] = 0;
+        word |= w;
+    }
+    return word;
+}
+
+// The latched error word, read (synchronises the stream) and cleared: *word = 0 when nothing was latched.  What a raised bit means is
 // the family's to say.
 inline int take_latched(HostCore *h, int32_t *word) {
     *word = 0;
-    MXV_HIP(h, hipMemcpyAsync(word, h->err, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     MXV_HIP(h, hipStreamSynchronize(h->stream));
-    if (*word != 0) MXV_HIP(h, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
+    *word = take_latched_drained(h);
     return MXV_OK;
 }
 
@@ -268,7 +298,8 @@ inline void drain(HostCore *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
 }
 inline void free_core(HostCore *h, std::initializer_list<void *> family_buffers) {
-    for (void *p : {(void *)h->err, (void *)h->t_dev, (void *)h->seeds, (void *)h->ep_acc, (void *)h->st_ep_r, (void *)h->st_ep_l})
+    if (h->err_host) (void)hipHostFree((void *)h->err_host);
+    for (void *p : {(void *)h->t_dev, (void *)h->seeds, (void *)h->ep_acc, (void *)h->st_ep_r, (void *)h->st_ep_l})
         if (p) (void)hipFree(p);
     for (void *p : family_buffers)
         if (p) (void)hipFree(p);

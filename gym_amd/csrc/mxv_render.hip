@@ -426,7 +426,7 @@ struct RenderArgs {
     const int32_t *idx;    // [count] or nullptr (frame k = env k)
     uint8_t *frames;       // render_kernel: [count][H][W][3]
     int32_t *records;      // scene_kernel: [count][kMaxRec][kRec]
-    int32_t *err;
+    int32_t *err;          // the render kernels' own word of the handle's latch block (pinned host memory)
     const float *last_u;   // Pendulum: [N] or nullptr (no arrow)
     const uint4 *sat;      // Pendulum: the arrow's summed-area table [img_h + 1][img_w + 1]
     int64_t n;
@@ -435,6 +435,9 @@ struct RenderArgs {
     int32_t img_h, img_w;
     double P[MXV_MAX_PARAMS];
 };
+
+// The render word only ever receives this one bit: a plain store does what an atomic OR would, and no device atomic targets host memory.
+__device__ __forceinline__ void raise_render_error(int32_t *err) { *reinterpret_cast<volatile int32_t *>(err) = kRenderIndexErrorBit; }
 
 struct SceneLds {
     int32_t rec[kMaxRec][kRec];
@@ -458,7 +461,7 @@ __global__ __launch_bounds__(kThreads) void scene_kernel(RenderArgs a) {
     double s[4], P[MXV_MAX_PARAMS];
     float u;
     if (!load_env(a, frame, s, P, &u)) {
-        if (threadIdx.x == 0) atomicOr(a.err, kRenderIndexErrorBit);
+        if (threadIdx.x == 0) raise_render_error(a.err);
         for (int i = threadIdx.x; i < kMaxRec * kRec; i += blockDim.x) out[i] = 0;
         return;
     }
@@ -602,7 +605,7 @@ __global__ __launch_bounds__(kThreads) void render_kernel(RenderArgs a) {
     double s[4], P[MXV_MAX_PARAMS];
     float u;
     if (!load_env(a, frame, s, P, &u)) {
-        if (t == 0 && band == 0) atomicOr(a.err, kRenderIndexErrorBit);
+        if (t == 0 && band == 0) raise_render_error(a.err);
         for (int run = t; run < runs; run += kThreads) store_run(o4 + 3 * run, 0u);
         return;
     }
@@ -713,7 +716,7 @@ __global__ __launch_bounds__(kThreads) void pixels_kernel(PixelArgs a) {
     double s[4], P[MXV_MAX_PARAMS];
     float u;
     if (!load_env(a.r, frame, s, P, &u)) {
-        if (t == 0 && band == 0) atomicOr(a.r.err, kRenderIndexErrorBit);
+        if (t == 0 && band == 0) raise_render_error(a.r.err);
         store_band(a, dst0, nb, nullptr, 0);
         return;
     }

@@ -771,7 +771,7 @@ int mxv_tab_create(const mxv_tab_config *cfg, const double *cum_prob_host, const
     h->own_stream = true;
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->state, n * sizeof(int32_t)));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->elapsed, n * sizeof(int32_t)));
-    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->err, sizeof(int32_t)));
+    MXV_CREATE_HIP(h, mxv_tab_destroy, alloc_latch(h));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->t_dev, sizeof(uint64_t)));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->reward, entries * sizeof(double)));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->nt, entries * sizeof(int32_t)));
@@ -780,7 +780,6 @@ int mxv_tab_create(const mxv_tab_config *cfg, const double *cum_prob_host, const
     if (!all_one) MXV_CREATE_HIP(h, mxv_tab_destroy, hipMalloc((void **)&h->prob, entries * sizeof(double)));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->state, 0, n * sizeof(int32_t), h->stream));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->elapsed, 0, n * sizeof(int32_t), h->stream));
-    MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->err, 0, sizeof(int32_t), h->stream));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemsetAsync(h->t_dev, 0, sizeof(uint64_t), h->stream));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->reward, reward_host, entries * sizeof(double), hipMemcpyHostToDevice, h->stream));
     MXV_CREATE_HIP(h, mxv_tab_destroy, hipMemcpyAsync(h->nt, packed.data(), entries * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));

@@ -126,12 +126,15 @@ class ShardedRollout:
         self._layout = None
         # Snapshots of the chunk's final tensors, TWO sets used alternately: the fused rollout kernel deposits the last step's
         # outputs into the armed set itself (mxv_set_final_snapshot), the gather reads it while the next chunk — armed with the
-        # other set — already runs.  Engines without that hook (the CPU stand-in of the gloo tests) get copies instead.
+        # other set — already runs.  Engines without that hook (the CPU stand-in of the gloo tests) get copies instead.  The kernel is
+        # armed only once a gather has been asked for on this object: a job that never gathers never pays the second set of stores
+        # (26 B per env and launch for CartPole).  The first gather_async() copies the finals and switches arming on.
         self._snap = None
         self._works = [None, None]
         self._cur = 0
         self._cur_written = False     # the most recent rollout deposited its finals into set _cur
-        self._cur_gathered = True     # set _cur has been handed to a gather since it was written (=> the next rollout flips sets)
+        self._cur_gathered = False    # set _cur has been handed to a gather since it was written (=> the next rollout flips sets)
+        self._armed = False           # a gather has been requested: rollouts deposit their finals in-kernel from now on
         handle = getattr(self.engine, "handle", None)
         self._in_kernel = handle is not None and hasattr(handle, "set_final_snapshot")
         self._force_collective = False   # measurement hook (tools/chunk_overhead.py): issue the real collective at world size 1 too
@@ -205,7 +208,7 @@ class ShardedRollout:
 
     def _arm(self, K: int = 2):
         """Called before every rollout: pick the snapshot set this rollout deposits its final tensors into."""
-        if not self._in_kernel:
+        if not self._in_kernel or not self._armed:
             self._cur_written = False
             return
         snap = self._snapshots()
@@ -247,6 +250,7 @@ class ShardedRollout:
             self._pending = ("torch", self._cur)
         self._cur_gathered = True
         self._cur_written = False
+        self._armed = True
 
     def wait_gather(self):
         """GatheredOutputs of the last gather_async (unpacks to the full (N_total, ...) obs / reward / terminated /

@@ -27,6 +27,10 @@ typedef struct mxv_launch_info {
     uint32_t grid, block;
 } mxv_launch_info;
 int mxv_last_launch(mxv_handle *h, mxv_launch_info *out);
+/* The final snapshot (mxv_set_final_snapshot) as the handle holds it: *attached = buffers are attached now; *deposited = the handle's last
+ * step / rollout launch was handed them as kernel arguments (the fused rollout kernel wrote the last step's outputs a second time; 0 for
+ * launches that copy the snapshot afterwards or have none).  Either pointer may be NULL, not both. */
+int mxv_last_launch_snapshot(mxv_handle *h, int32_t *attached, int32_t *deposited);
 
 
 /* -- diagnostics ------------------------------------------------------------------------------------------------------------------
