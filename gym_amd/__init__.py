@@ -30,6 +30,8 @@ _LAZY = {
     "BlackjackRollout": ("gym_amd.toy_text", "BlackjackRollout"),
     "gae": ("gym_amd.returns", "gae"),
     "discounted_returns": ("gym_amd.returns", "discounted_returns"),
+    "sample_categorical": ("gym_amd.policy", "sample_categorical"),
+    "PolicySampler": ("gym_amd.policy", "PolicySampler"),
 }
 
 

@@ -76,6 +76,19 @@ class _RolloutBase:
         return discounted_returns(traj["reward"], traj["terminated"], traj["truncated"], gamma=gamma, last_value=last_value,
                                   final_values=final_values, out=out)
 
+    def policy_sampler(self, seed=None):
+        """A gym_amd.policy.PolicySampler for this rollout's actions: its action count and dtype, its env_offset (so that shards of one
+        logical vector env draw what the whole would), on its device; `seed` defaults to the rollout's action_seed.
+        sampler.sample(logits)[0] is what step() takes (DeviceRollout), and with [None] in front the K = 1 tape of rollout_tape()."""
+        from .policy import PolicySampler
+
+        n, dtype = self._policy_head
+        if n < 1:
+            raise ValueError(f"{type(self).__name__}: policy_sampler() draws Discrete actions; this env takes Box actions "
+                             "(a Gaussian head is a follow-up: DESIGN.md §12)")
+        return PolicySampler(n, seed=self.handle._action_seed if seed is None else seed, env_offset=self.env_offset, action_dtype=dtype,
+                             device=self.device)
+
     def synchronize(self):
         """Wait for the engine's stream; raises if a step saw an out-of-range action."""
         try:

@@ -62,6 +62,8 @@ class DeviceRollout(_RolloutBase):
             self.action_dtype = torch.int32 if action_i32 else torch.int64
         else:
             self.action_dtype = torch.float32
+        self.env_offset = int(env_offset)
+        self._policy_head = (self.NA, self.action_dtype)      # policy_sampler(): Discrete action count (0: Box) and dtype
         with torch.cuda.stream(self.stream):
             n = self.num_envs
             self.obs = torch.empty((n, self.O), dtype=torch.float32, device=self.device)

@@ -417,6 +417,8 @@ class TabularRollout(_RolloutBase):
         self.int_dtype, self.real_dtype = (torch.int32, torch.float32) if compact else (torch.int64, torch.float64)
         self._adopt(_make_handle(self.mdp, num_envs, limit, device, env_offset, seed, action_seed, compact=compact,
                                  general_kernel=general_kernel))
+        self.env_offset = int(env_offset)
+        self._policy_head = (self.mdp.num_actions, self.int_dtype)      # policy_sampler(): what rollout_tape() takes
         with torch.cuda.stream(self.stream):
             self.obs = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
         self.stream.synchronize()
@@ -470,6 +472,8 @@ class BlackjackRollout(_RolloutBase):
         self.int_dtype, self.real_dtype = (torch.int32, torch.float32) if compact else (torch.int64, torch.float64)
         self._adopt(_native.Blackjack(self.num_envs, natural=natural, sab=sab, device=device, env_offset=env_offset, seed=seed,
                                       action_seed=action_seed, max_episode_steps=-1 if max_episode_steps is None else max_episode_steps))
+        self.env_offset = int(env_offset)
+        self._policy_head = (2, torch.int64)      # policy_sampler(): stick / hit; rollout_tape() takes int64
         with torch.cuda.stream(self.stream):
             self.obs = torch.zeros((3, self.num_envs), dtype=torch.int64, device=self.device)
         self.stream.synchronize()

@@ -35,6 +35,9 @@
  *             consumes its own reset stream in order, like the per-env generator of the reference (cartpole.py:202).  The
  *             ordinals are device state (uint32 [N]): mxv_get_episodes / mxv_set_episodes for checkpoints.
  *             uniform(low, high) = low + (high-low)*(word+0.5)*2^-32 in fp64, one word per state component.
+ *   policy draws (mxv_policy.h, optional): key = the sampler's seed, ctr = (g_lo, g_hi, t_lo, (t_hi & 0x0fffffff) | 7<<28), one word per
+ *             env and policy step t: u = (word+0.5)*2^-32 picks the action from the cumulative softmax sums (the rule is in that header)
+ *   stream tags in ctr[3] >> 28: 1 actions, 2 resets, 3 tabular transitions, 4 step noise, 5 Blackjack draws, 6 action bits, 7 policy draws
  * t = index of the vector step since the last mxv_seed().  Streams use GLOBAL env indices: any sharding of one logical vector env
  * over several handles / GPUs draws the same numbers.
  *

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""The constants of EXP and LOG in include/mxv_policy.h, generated: every one is an exact fraction — or ln 2 / 1/ln 2 /
+sqrt(1/2) from 200-digit integer arithmetic — rounded once, to nearest even, to double.  Prints the C++ block that
+gym_amd/csrc/mxv_policy.hip carries verbatim (tests/test_policy_host.py compares the two and the NumPy twin against this module).
+
+    python tools/policy_coefficients.py            # the block
+"""
+from fractions import Fraction
+from math import factorial, isqrt
+
+EXP_DEGREE = 13      # EXP: sum_{j=0}^{13} r^j / j!          on |r| <= ln2 / 2
+LOG_TERMS = 12       # LOG: 2 s sum_{j=0}^{11} z^j / (2j+1)  on |s| <= 3 - 2 sqrt 2, z = s s
+LN2_HI_BITS = 32     # ln2_hi keeps the first 32 significant bits of ln 2: k * ln2_hi is exact for |k| < 2^21
+
+_SCALE = 10 ** 200
+
+
+def _ln2() -> Fraction:
+    """ln 2 = 2 atanh(1/3) = 2 sum 1 / ((2j+1) 3^(2j+1)), to better than 10^-200."""
+    total, j = Fraction(0), 0
+    while True:
+        term = Fraction(1, (2 * j + 1) * 3 ** (2 * j + 1))
+        if term * _SCALE * 1000 < 1:
+            break
+        total += term
+        j += 1
+    return 2 * total
+
+
+def _sqrt_half() -> Fraction:
+    return Fraction(isqrt(_SCALE * _SCALE // 2), _SCALE)
+
+
+def _truncate(x: Fraction, bits: int) -> Fraction:
+    """x with its first `bits` significant bits kept (towards zero)."""
+    e = 0
+    while x * Fraction(2) ** -e >= 1:
+        e += 1
+    while x * Fraction(2) ** -e < Fraction(1, 2):
+        e -= 1
+    m = int(x * Fraction(2) ** (bits - e))
+    return Fraction(m) * Fraction(2) ** (e - bits)
+
+
+def constants() -> dict:
+    """name -> float (float(Fraction) rounds correctly)."""
+    ln2 = _ln2()
+    hi = _truncate(ln2, LN2_HI_BITS)
+    return {
+        "inv_ln2": float(1 / ln2),
+        "ln2_hi": float(hi),
+        "ln2_lo": float(ln2 - hi),
+        "sqrt_half": float(_sqrt_half()),
+        "exp_c": [float(Fraction(1, factorial(j))) for j in range(EXP_DEGREE + 1)],      # index j: 1 / j!
+        "log_c": [float(Fraction(1, 2 * j + 1)) for j in range(LOG_TERMS)],               # index j: 1 / (2j+1)
+    }
+
+
+def block() -> str:
+    c = constants()
+    lines = [f"constexpr double kInvLn2 = {c['inv_ln2'].hex()};",
+             f"constexpr double kLn2Hi = {c['ln2_hi'].hex()};",
+             f"constexpr double kLn2Lo = {c['ln2_lo'].hex()};",
+             f"constexpr double kSqrtHalf = {c['sqrt_half'].hex()};",
+             f"constexpr double kExpC[{EXP_DEGREE + 1}] = {{" + ", ".join(x.hex() for x in c["exp_c"]) + "};",
+             f"constexpr double kLogC[{LOG_TERMS}] = {{" + ", ".join(x.hex() for x in c["log_c"]) + "};"]
+    return "\n".join(lines)
+
+
+if __name__ == "__main__":
+    print(block())
