@@ -32,6 +32,8 @@ _LAZY = {
     "discounted_returns": ("gym_amd.returns", "discounted_returns"),
     "sample_categorical": ("gym_amd.policy", "sample_categorical"),
     "PolicySampler": ("gym_amd.policy", "PolicySampler"),
+    "sample_gaussian": ("gym_amd.policy", "sample_gaussian"),
+    "GaussianSampler": ("gym_amd.policy", "GaussianSampler"),
 }
 
 

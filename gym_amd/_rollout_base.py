@@ -84,10 +84,22 @@ class _RolloutBase:
 
         n, dtype = self._policy_head
         if n < 1:
-            raise ValueError(f"{type(self).__name__}: policy_sampler() draws Discrete actions; this env takes Box actions "
-                             "(a Gaussian head is a follow-up: DESIGN.md §12)")
+            raise ValueError(f"{type(self).__name__}: policy_sampler() draws Discrete actions; this env takes Box actions: "
+                             "use gaussian_sampler() for a Gaussian head (DESIGN.md §13)")
         return PolicySampler(n, seed=self.handle._action_seed if seed is None else seed, env_offset=self.env_offset, action_dtype=dtype,
                              device=self.device)
+
+    def gaussian_sampler(self, seed=None):
+        """A gym_amd.policy.GaussianSampler for this rollout's Box actions (one dim): its env_offset (so that shards of one logical vector
+        env draw what the whole would), on its device; `seed` defaults to the rollout's action_seed.
+        sampler.sample(mean, log_std)[0] is what step() takes."""
+        from .policy import GaussianSampler
+
+        n, _ = self._policy_head
+        if n >= 1:
+            raise ValueError(f"{type(self).__name__}: gaussian_sampler() draws Box actions; this env takes Discrete({n}) actions: "
+                             "use policy_sampler()")
+        return GaussianSampler(1, seed=self.handle._action_seed if seed is None else seed, env_offset=self.env_offset, device=self.device)
 
     def synchronize(self):
         """Wait for the engine's stream; raises if a step saw an out-of-range action."""

@@ -127,7 +127,7 @@ constexpr uint32_t kStreamAction = 1u;
 constexpr uint32_t kStreamReset = 2u;
 constexpr uint32_t kStreamStepNoise = 4u;  // (3 = the tabular engine's transition stream, 5 = Blackjack's draw stream)
 constexpr uint32_t kStreamActionBits = 6u; // Discrete(2) action stream of the classic engine: one bit per step
-// (7 = the policy draws of mxv_policy.hip: kStreamPolicy there)
+// (7 = the policy draws of mxv_policy.hip: kStreamPolicy there; 8 = the Gaussian draws of mxv_gaussian.hip: kStreamGaussian)
 
 // u in (0,1): (w + 0.5) * 2^-32, exact in fp64.
 __device__ __forceinline__ double u01(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }

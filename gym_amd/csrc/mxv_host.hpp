@@ -45,6 +45,10 @@ const char *last_error(const H *h) {
     return h ? h->error.c_str() : create_error<H>().c_str();
 }
 
+// fail() into the per-thread error slot of the handle-free calls of include/mxv_policy.h, which mxv_policy_last_error reports.  The slot
+// lives in mxv_policy.hip; mxv_gaussian.hip records its messages through this.  Not part of the library's dynamic symbol table.
+__attribute__((visibility("hidden"), format(printf, 2, 3))) int policy_call_fail(int code, const char *fmt, ...);
+
 // Caller-owned tensors on their element's natural boundary: an odd address would not fault on this device (unaligned global access is
 // enabled) but tears every coalesced burst, and it is a caller bug either way — refused up front with the tensor's name
 // (tests/c_consumer/abi_fuzz.c).

@@ -230,6 +230,15 @@ hipError_t launch(dim3 grid, hipStream_t st, PolicyArgs &a) {
 
 }  // namespace
 
+int mxv::policy_call_fail(int code, const char *fmt, ...) {   // mxv_host.hpp: the same slot for mxv_gaussian.hip
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return mxv::fail<PolicyCall>(nullptr, code, "%s", buf);
+}
+
 extern "C" {
 
 int mxv_policy_sample_categorical(void *stream, int64_t N, int32_t A, const float *logits_dev, int64_t ld, uint64_t seed,
