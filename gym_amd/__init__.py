@@ -34,6 +34,8 @@ _LAZY = {
     "PolicySampler": ("gym_amd.policy", "PolicySampler"),
     "sample_gaussian": ("gym_amd.policy", "sample_gaussian"),
     "GaussianSampler": ("gym_amd.policy", "GaussianSampler"),
+    "evaluate_categorical": ("gym_amd.policy_eval", "evaluate_categorical"),
+    "evaluate_gaussian": ("gym_amd.policy_eval", "evaluate_gaussian"),
 }
 
 

@@ -175,6 +175,15 @@ class PolicySampler:
         return sample_categorical(logits, seed=self.seed, step=self._step, env_offset=self.env_offset, action_dtype=self.action_dtype,
                                   out=out)
 
+    def evaluate(self, logits, actions, out=None):
+        """-> (log_prob, entropy) of stored `actions` under `logits`, differentiable: gym_amd.policy_eval.evaluate_categorical().  Draws
+        nothing and leaves the stream where it is."""
+        from .policy_eval import evaluate_categorical
+
+        if isinstance(logits, self._torch.Tensor) and logits.dim() >= 2 and logits.shape[-1] != self.num_actions:
+            raise ValueError(f"logits must have {self.num_actions} columns (num_actions), got {tuple(logits.shape)}")
+        return evaluate_categorical(logits, actions, out=out)
+
     def step_index(self) -> int:
         """How many draws the stream has made (synchronises)."""
         return int(self._step.item()) & _U64
@@ -296,6 +305,15 @@ class GaussianSampler:
         if isinstance(mean, self._torch.Tensor) and mean.dim() == 2 and mean.shape[1] != self.action_dim:
             raise ValueError(f"mean must have {self.action_dim} columns (action_dim), got {tuple(mean.shape)}")
         return sample_gaussian(mean, log_std, seed=self.seed, step=self._step, env_offset=self.env_offset, out=out)
+
+    def evaluate(self, mean, log_std, actions, out=None):
+        """-> (log_prob, entropy) of stored `actions` under (mean, log_std), differentiable: gym_amd.policy_eval.evaluate_gaussian().  Draws
+        nothing and leaves the stream where it is."""
+        from .policy_eval import evaluate_gaussian
+
+        if isinstance(mean, self._torch.Tensor) and mean.dim() >= 2 and mean.shape[-1] != self.action_dim:
+            raise ValueError(f"mean must have {self.action_dim} columns (action_dim), got {tuple(mean.shape)}")
+        return evaluate_gaussian(mean, log_std, actions, out=out)
 
     def step_index(self) -> int:
         """How many draws the stream has made (synchronises)."""
