@@ -4,7 +4,8 @@
 // the object, or — for a NULL object, i.e. a failed create — in a per-thread slot of that object TYPE, which its *_last_error(NULL)
 // reports.  HostCore: what the three engine handles (classic control, tabular, Blackjack) keep alike — device, stream, error word,
 // step / reset counters and the device clock, seeds, episode statistics — and the calls that only touch it.  Each exported function
-// stays a short forwarder in its family's file; a step only one family needs stays there too.  Host code only: no kernels here.
+// stays a short forwarder in its family's file; a step only one family needs stays there too.  The handle-free policy calls have their
+// own slots and argument checks in mxv_policy_host.hpp.  Host code only: no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,10 +45,6 @@ template <class H>
 const char *last_error(const H *h) {
     return h ? h->error.c_str() : create_error<H>().c_str();
 }
-
-// fail() into the per-thread error slot of the handle-free calls of include/mxv_policy.h, which mxv_policy_last_error reports.  The slot
-// lives in mxv_policy.hip; mxv_gaussian.hip records its messages through this.  Not part of the library's dynamic symbol table.
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int policy_call_fail(int code, const char *fmt, ...);
 
 // Caller-owned tensors on their element's natural boundary: an odd address would not fault on this device (unaligned global access is
 // enabled) but tears every coalesced burst, and it is a caller bug either way — refused up front with the tensor's name

@@ -2,6 +2,8 @@
 //
 // The result is defined bit for bit by the rule in the header: float64, one rounding per operation (this file is built with
 // -ffp-contract=off like the rest of the library), EXP and LOG as the operation sequences written there — no libm call, no __expf.
+// Their one text, with the constants, the limits and the launch shape, is mxv_policy_rule.hpp, which mxv_gaussian.hip and
+// mxv_policy_eval.hip include too; the argument checks and the error slot are those of mxv_policy_host.hpp.
 //
 // Shape of the kernel (arithmetic bound: ~45 fp64 operations per logit and a Philox call per env against 4 A + 16 bytes):
 //   * one lane owns one env.  For A = 2, 3, 4, 6 — the engine's own action counts — a straight-line instantiation holds the row, its
@@ -20,26 +22,15 @@
 #include <string>
 
 #include "../../include/mxv_policy.h"
-#include "mxv_device.hpp"
-#include "mxv_host.hpp"
+#include "mxv_policy_host.hpp"
+#include "mxv_policy_rule.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 2048;    // 256 CUs x 8 workgroups of 4 waves = every wave slot
-constexpr int kMaxActions = 64;
-constexpr int64_t kMaxElems = (int64_t)1 << 40;
-constexpr uint32_t kStreamPolicy = 7u;   // 1-6: mxv_device.hpp (kStream*), mxv_tab.hip, mxv_bj.hip
+using namespace mxv::rule;
+using namespace mxv::policy_host;
 
-// ---- the constants of EXP and LOG: the output of tools/policy_coefficients.py, verbatim ----
-constexpr double kInvLn2 = 0x1.71547652b82fep+0;
-constexpr double kLn2Hi = 0x1.62e42fee00000p-1;
-constexpr double kLn2Lo = 0x1.a39ef35793c76p-33;
-constexpr double kSqrtHalf = 0x1.6a09e667f3bcdp-1;
-constexpr double kExpC[14] = {0x1.0000000000000p+0, 0x1.0000000000000p+0, 0x1.0000000000000p-1, 0x1.5555555555555p-3, 0x1.5555555555555p-5, 0x1.1111111111111p-7, 0x1.6c16c16c16c17p-10, 0x1.a01a01a01a01ap-13, 0x1.a01a01a01a01ap-16, 0x1.71de3a556c734p-19, 0x1.27e4fb7789f5cp-22, 0x1.ae64567f544e4p-26, 0x1.1eed8eff8d898p-29, 0x1.6124613a86d09p-33};
-constexpr double kLogC[12] = {0x1.0000000000000p+0, 0x1.5555555555555p-2, 0x1.999999999999ap-3, 0x1.2492492492492p-3, 0x1.c71c71c71c71cp-4, 0x1.745d1745d1746p-4, 0x1.3b13b13b13b14p-4, 0x1.1111111111111p-4, 0x1.e1e1e1e1e1e1ep-5, 0x1.af286bca1af28p-5, 0x1.8618618618618p-5, 0x1.642c8590b2164p-5};
-// ---- end of the generated block ----
-constexpr double kExpCut = -708.0;
+constexpr uint32_t kStreamPolicy = 7u;   // 1-6: mxv_device.hpp (kStream*), mxv_tab.hip, mxv_bj.hip
 
 struct PolicyArgs {
     const float *logits;
@@ -51,36 +42,7 @@ struct PolicyArgs {
     int32_t A, i64;
 };
 
-__device__ __forceinline__ double exp_rule(double d) {   // -708 <= d <= 0
-    const double k = __builtin_rint(d * kInvLn2);
-    const double r = (d - k * kLn2Hi) - k * kLn2Lo;
-    double p = kExpC[13];
-#pragma unroll
-    for (int j = 12; j >= 0; --j) p = p * r + kExpC[j];
-    return __builtin_ldexp(p, (int)k);
-}
-
-__device__ __forceinline__ double e_of(double d) { return d < kExpCut ? 0.0 : exp_rule(d < kExpCut ? 0.0 : d); }
-
-__device__ __forceinline__ double log_rule(double S) {   // 1 <= S <= 64
-    int e;
-    double f = __builtin_frexp(S, &e);
-    if (f < kSqrtHalf) {
-        f = f * 2.0;
-        e = e - 1;
-    }
-    const double ed = (double)e;
-    const double s = (f - 1.0) / (f + 1.0);
-    const double z = s * s;
-    double p = kLogC[11];
-#pragma unroll
-    for (int j = 10; j >= 0; --j) p = p * z + kLogC[j];
-    return ((ed * kLn2Hi) + (2.0 * s) * p) + ed * kLn2Lo;
-}
-
 __device__ __forceinline__ float to_f32(double x) { return (float)x; }   // round to nearest even; the NaN rows are written as a pattern
-
-__device__ __forceinline__ bool bad_logit(float x) { return x != x || x == __builtin_inff(); }
 
 struct Draw {
     int32_t action;
@@ -196,22 +158,6 @@ __global__ void __launch_bounds__(kThreads) policy_kernel(const PolicyArgs a) {
     }
 }
 
-struct PolicyCall {   // the error slot of the handle-free call: one per thread (mxv::create_error)
-    std::string error;
-};
-
-template <typename... T>
-int bad(const char *fmt, T... args) {
-    return mxv::fail<PolicyCall>(nullptr, MXV_ERR_INVALID_ARG, fmt, args...);
-}
-
-struct Range {   // the bytes [lo, lo + bytes) of one argument; lo == 0: absent
-    const char *name;
-    uintptr_t lo;
-    uint64_t bytes;
-};
-bool meet(const Range &a, const Range &b) { return a.lo && b.lo && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes; }
-
 struct LastLaunch {   // of the calling thread (mxv_policy_last_launch)
     int32_t envs_per_lane = 0, specialised_A = 0;
     uint32_t grid = 0;
@@ -222,85 +168,48 @@ LastLaunch &last_launch() {
 }
 
 template <int AT>
-hipError_t launch(dim3 grid, hipStream_t st, PolicyArgs &a) {
-    void *args[] = {&a};
-    // hipLaunchKernel returns THIS launch's status (hipGetLastError would also report, and clear, an earlier call's error)
-    return hipLaunchKernel(reinterpret_cast<const void *>(&policy_kernel<AT>), grid, dim3(kThreads), args, 0, st);
+const void *kernel_of() {
+    return reinterpret_cast<const void *>(&policy_kernel<AT>);
 }
 
 }  // namespace
-
-int mxv::policy_call_fail(int code, const char *fmt, ...) {   // mxv_host.hpp: the same slot for mxv_gaussian.hip
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return mxv::fail<PolicyCall>(nullptr, code, "%s", buf);
-}
 
 extern "C" {
 
 int mxv_policy_sample_categorical(void *stream, int64_t N, int32_t A, const float *logits_dev, int64_t ld, uint64_t seed,
                                   uint64_t env_offset, uint64_t step, uint64_t *step_dev, void *actions_dev, int32_t actions_are_i64,
                                   float *log_prob_dev, float *entropy_dev) {
-    const char *api = "mxv_policy_sample_categorical";
-    if (!logits_dev) return bad("%s: logits pointer is NULL", api);
-    if (!actions_dev) return bad("%s: actions pointer is NULL", api);
-    if (N < 1) return bad("%s: N = %lld must be at least 1", api, (long long)N);
-    if (A < 1 || A > kMaxActions) return bad("%s: A = %d must be in 1..%d", api, (int)A, kMaxActions);
-    if (ld < A) return bad("%s: row stride ld = %lld must be at least A = %d", api, (long long)ld, (int)A);
-    if (ld > kMaxElems / N) return bad("%s: N * ld = %lld * %lld is beyond 2^40 elements", api, (long long)N, (long long)ld);
+    const Call<mxv::PolicyCall> call{"mxv_policy_sample_categorical", 'N'};
+    if (int rc = call.check_cat(N, A, logits_dev, ld, actions_dev)) return rc;
     const uint64_t ab = actions_are_i64 ? 8 : 4;
-    const Range logits{"logits", (uintptr_t)logits_dev, ((uint64_t)(N - 1) * (uint64_t)ld + (uint64_t)A) * 4};
-    const Range stepr{"step_dev", (uintptr_t)step_dev, 8};
-    const Range outs[] = {{"actions", (uintptr_t)actions_dev, (uint64_t)N * ab}, {"log_prob", (uintptr_t)log_prob_dev, (uint64_t)N * 4},
-                          {"entropy", (uintptr_t)entropy_dev, (uint64_t)N * 4}};
-    struct Aligned {
-        const Range *r;
-        uint64_t elem;
-    };
-    for (const Aligned &x : {Aligned{&logits, 4}, Aligned{&stepr, 8}, Aligned{&outs[0], ab}, Aligned{&outs[1], 4}, Aligned{&outs[2], 4}}) {
-        if (x.r->lo & (x.elem - 1)) return bad("%s: %s pointer %p is not %llu-byte aligned", api, x.r->name, (void *)x.r->lo, (unsigned long long)x.elem);
-        if (x.r->lo && x.r->bytes > UINTPTR_MAX - x.r->lo)
-            return bad("%s: %s at %p with N = %lld does not fit the address space", api, x.r->name, (void *)x.r->lo, (long long)N);
-    }
-    for (int i = 0; i < 3; ++i) {
-        if (meet(outs[i], logits)) return bad("%s: output %s overlaps the logits", api, outs[i].name);
-        if (meet(outs[i], stepr)) return bad("%s: output %s overlaps step_dev", api, outs[i].name);
-        for (int j = i + 1; j < 3; ++j)
-            if (meet(outs[i], outs[j])) return bad("%s: outputs %s and %s overlap", api, outs[i].name, outs[j].name);
-    }
-
+    const Range ins[] = {{"logits", (uintptr_t)logits_dev, rows_bytes(N, ld, A), 4}, {"step_dev", (uintptr_t)step_dev, 8, 8, ""}};
+    const Range outs[] = {{"actions", (uintptr_t)actions_dev, (uint64_t)N * ab, ab}, {"log_prob", (uintptr_t)log_prob_dev, (uint64_t)N * 4, 4},
+                          {"entropy", (uintptr_t)entropy_dev, (uint64_t)N * 4, 4}};
+    if (int rc = call.check_ranges(N, ins, 2, outs, 3)) return rc;
     PolicyArgs a;
     a.logits = logits_dev; a.step_dev = step_dev; a.actions = actions_dev; a.log_prob = log_prob_dev; a.entropy = entropy_dev;
     a.N = N; a.ld = ld; a.tiles = (N + kThreads - 1) / kThreads;
     a.seed = seed; a.env_offset = env_offset; a.step = step;
     a.A = A; a.i64 = actions_are_i64 ? 1 : 0;
-    const dim3 grid((unsigned)(a.tiles < kMaxBlocks ? a.tiles : kMaxBlocks));
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
+    const void *kernel;
     int32_t spec = A;
     switch (A) {
-        case 2: e = launch<2>(grid, st, a); break;
-        case 3: e = launch<3>(grid, st, a); break;
-        case 4: e = launch<4>(grid, st, a); break;
-        case 6: e = launch<6>(grid, st, a); break;
-        default: e = launch<0>(grid, st, a); spec = 0; break;
+        case 2: kernel = kernel_of<2>(); break;
+        case 3: kernel = kernel_of<3>(); break;
+        case 4: kernel = kernel_of<4>(); break;
+        case 6: kernel = kernel_of<6>(); break;
+        default: kernel = kernel_of<0>(); spec = 0; break;
     }
-    if (e != hipSuccess) return mxv::fail<PolicyCall>(nullptr, MXV_ERR_HIP, "%s: kernel launch: %s", api, hipGetErrorString(e));
-    if (step_dev) {
-        e = mxv::launch_add_word(step_dev, 1, st);
-        if (e != hipSuccess) return mxv::fail<PolicyCall>(nullptr, MXV_ERR_HIP, "%s: step counter launch: %s", api, hipGetErrorString(e));
-    }
-    last_launch() = LastLaunch{1, spec, grid.x};
+    if (int rc = call.launch(kernel, a, stream)) return rc;
+    if (int rc = call.advance(step_dev, stream)) return rc;
+    last_launch() = LastLaunch{1, spec, grid_of(a.tiles).x};
     return MXV_OK;
 }
 
-const char *mxv_policy_last_error(void) { return mxv::last_error<PolicyCall>(nullptr); }
+const char *mxv_policy_last_error(void) { return mxv::last_error<mxv::PolicyCall>(nullptr); }
 
 int mxv_policy_last_launch(int32_t *envs_per_lane, int32_t *specialised_A, uint32_t *grid) {
-    if (!envs_per_lane || !specialised_A || !grid) return bad("mxv_policy_last_launch: output pointer is NULL");
+    if (!envs_per_lane || !specialised_A || !grid) return mxv::fail<mxv::PolicyCall>(nullptr, MXV_ERR_INVALID_ARG, "mxv_policy_last_launch: output pointer is NULL");
     *envs_per_lane = last_launch().envs_per_lane;
     *specialised_A = last_launch().specialised_A;
     *grid = last_launch().grid;

@@ -3,8 +3,9 @@
 //
 // The results are defined bit for bit by the rule in the header: float64, one rounding per operation (this file is built with
 // -ffp-contract=off like the rest of the library), EXP and LOG as the operation sequences of include/mxv_policy.h — no libm call — and
-// IEEE `/`.  The forward lines are those of mxv_policy.hip / mxv_gaussian.hip, so a stored action re-evaluated under the head that drew
-// it gets the sampler's bits.
+// IEEE `/`.  EXP, LOG, the constants and the degenerate-row tests are the text that mxv_policy.hip and mxv_gaussian.hip include as well
+// (mxv_policy_rule.hpp), and the forward lines around them are the samplers', so a stored action re-evaluated under the head that drew
+// it gets the sampler's bits.  The argument checks are those of mxv_policy_host.hpp.
 //
 // Shape of the kernels (arithmetic bound: ~45 fp64 operations per logit, ~45 per Gaussian dim, against 4 A + 12 or 12 D + 8 bytes a row):
 //   * one lane owns one row.  Categorical, A = 2, 3, 4, 6: a straight-line instantiation holds the row, its d_a and e_a in registers and
@@ -25,34 +26,13 @@
 #include <string>
 
 #include "../../include/mxv_policy_eval.h"
-#include "mxv_host.hpp"
+#include "mxv_policy_host.hpp"
+#include "mxv_policy_rule.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 2048;    // 256 CUs x 8 workgroups of 4 waves = every wave slot
-constexpr int kMaxActions = 64;
-constexpr int kMaxDim = 4;
-constexpr int64_t kMaxElems = (int64_t)1 << 40;
-constexpr double kExpCut = -708.0;
-constexpr double kLogStdMax = 80.0;        // sigma = EXP(+-80) is a normal float32
-
-// ---- the constants of the rule: the output of tools/gaussian_coefficients.py, verbatim ----
-constexpr double kInvLn2 = 0x1.71547652b82fep+0;
-constexpr double kLn2Hi = 0x1.62e42fee00000p-1;
-constexpr double kLn2Lo = 0x1.a39ef35793c76p-33;
-constexpr double kSqrtHalf = 0x1.6a09e667f3bcdp-1;
-constexpr double kExpC[14] = {0x1.0000000000000p+0, 0x1.0000000000000p+0, 0x1.0000000000000p-1, 0x1.5555555555555p-3, 0x1.5555555555555p-5, 0x1.1111111111111p-7, 0x1.6c16c16c16c17p-10, 0x1.a01a01a01a01ap-13, 0x1.a01a01a01a01ap-16, 0x1.71de3a556c734p-19, 0x1.27e4fb7789f5cp-22, 0x1.ae64567f544e4p-26, 0x1.1eed8eff8d898p-29, 0x1.6124613a86d09p-33};
-constexpr double kLogC[12] = {0x1.0000000000000p+0, 0x1.5555555555555p-2, 0x1.999999999999ap-3, 0x1.2492492492492p-3, 0x1.c71c71c71c71cp-4, 0x1.745d1745d1746p-4, 0x1.3b13b13b13b14p-4, 0x1.1111111111111p-4, 0x1.e1e1e1e1e1e1ep-5, 0x1.af286bca1af28p-5, 0x1.8618618618618p-5, 0x1.642c8590b2164p-5};
-constexpr double kPio2Hi = 0x1.921fa00000000p+0;
-constexpr double kPio2Lo = 0x1.54442d184698ap-20;
-constexpr double kHalfLog2Pi = 0x1.d67f1c864beb5p-1;
-constexpr double kEntC = 0x1.6b3f8e4325f5ap+0;
-constexpr double kSinC[9] = {-0x1.5555555555555p-3, 0x1.1111111111111p-7, -0x1.a01a01a01a01ap-13, 0x1.71de3a556c734p-19, -0x1.ae64567f544e4p-26, 0x1.6124613a86d09p-33, -0x1.ae7f3e733b81fp-41, 0x1.952c77030ad4ap-49, -0x1.2f49b46814157p-57};
-constexpr double kCosC[10] = {-0x1.0000000000000p-1, 0x1.5555555555555p-5, -0x1.6c16c16c16c17p-10, 0x1.a01a01a01a01ap-16, -0x1.27e4fb7789f5cp-22, 0x1.1eed8eff8d898p-29, -0x1.93974a8c07c9dp-37, 0x1.ae7f3e733b81fp-45, -0x1.6827863b97d97p-53, 0x1.e542ba4020225p-62};
-// ---- end of the generated block ----
-// The block is the generator's whole output; no pass here draws a normal, so the SINCOS2PI constants in it have no other use than this.
-static_assert(kPio2Hi > kPio2Lo && kSinC[0] < 0.0 && kCosC[0] < 0.0, "the generated block");
+using namespace mxv::rule;
+using namespace mxv::policy_host;
 
 struct CatArgs {
     const float *logits;
@@ -72,47 +52,17 @@ struct GaussArgs {
     int64_t M, mean_ld, log_std_ld, actions_ld, grad_mean_ld, grad_log_std_ld, tiles;
 };
 
-__device__ __forceinline__ double exp_rule(double d) {   // |d| <= 80 or -708 <= d <= 0
-    const double k = __builtin_rint(d * kInvLn2);
-    const double r = (d - k * kLn2Hi) - k * kLn2Lo;
-    double p = kExpC[13];
-#pragma unroll
-    for (int j = 12; j >= 0; --j) p = p * r + kExpC[j];
-    return __builtin_ldexp(p, (int)k);
-}
-
-__device__ __forceinline__ double e_of(double d) { return d < kExpCut ? 0.0 : exp_rule(d < kExpCut ? 0.0 : d); }
-
-__device__ __forceinline__ double log_inline(double S) {   // 1 <= S <= 64 here
-    int e;
-    double f = __builtin_frexp(S, &e);
-    const bool low = f < kSqrtHalf;
-    f = low ? f * 2.0 : f;
-    e = low ? e - 1 : e;
-    const double ed = (double)e;
-    const double s = (f - 1.0) / (f + 1.0);
-    const double z = s * s;
-    double p = kLogC[11];
-#pragma unroll
-    for (int j = 10; j >= 0; --j) p = p * z + kLogC[j];
-    return ((ed * kLn2Hi) + (2.0 * s) * p) + ed * kLn2Lo;
-}
-
 // LOG out of line (once per row).  Inlined, its 15 constants are hoisted out of the tile loop and kept live across it next to those of EXP
 // and the kernel's arguments: more scalar registers than the loop instantiations have without spilling one, and one wave per SIMD less for
 // the forward ones.  The straight-line backward instantiations inline it instead: there the call costs vector registers (every d_a and
 // e_a is live across it), 82 against 68 at A = 6.
-__device__ __attribute__((noinline)) double log_call(double S) { return log_inline(S); }
+__device__ __attribute__((noinline)) double log_call(double S) { return log_rule(S); }
 
 // round to nearest even; every NaN leaves as the one pattern
 __device__ __forceinline__ float to_f32(double x) {
     const float y = (float)x;
     return y != y ? __uint_as_float(0x7FC00000u) : y;
 }
-
-__device__ __forceinline__ bool bad_logit(float x) { return x != x || x == __builtin_inff(); }
-__device__ __forceinline__ bool bad_mean(float x) { return !(__builtin_fabsf(x) < __builtin_inff()); }                     // NaN, +-Inf
-__device__ __forceinline__ bool bad_log_std(float x) { return !(__builtin_fabsf(x) <= (float)kLogStdMax); }              // NaN, |x| > 80
 
 // the stored action of row i, or -1 for anything outside 0..A-1
 __device__ __forceinline__ int32_t action_of(const CatArgs &a, int64_t i, int A) {
@@ -159,7 +109,7 @@ __device__ __forceinline__ void cat_straight(const CatArgs &a, int64_t i) {
         S = S + e[k];
         T = e[k] == 0.0 ? T : T + e[k] * d[k];
     }
-    const double L = BWD ? log_inline(S) : log_call(S);
+    const double L = BWD ? log_rule(S) : log_call(S);
     const double H = L - T / S;
     if constexpr (!BWD) {
         double d_action = d[0];
@@ -340,82 +290,7 @@ __global__ void __launch_bounds__(kThreads) eval_gauss_bwd(const GaussArgs a) {
     }
 }
 
-// ---- host: the argument checks, before the device is touched ----
-struct EvalCall {   // the error slot of the handle-free calls of this header: one per thread (mxv::create_error)
-    std::string error;
-};
-
-template <typename... T>
-int bad(const char *fmt, T... args) {
-    return mxv::fail<EvalCall>(nullptr, MXV_ERR_INVALID_ARG, fmt, args...);
-}
-
-struct Range {   // the bytes [lo, lo + bytes) of one argument, of elements of `elem` bytes; lo == 0: absent
-    const char *name;
-    uintptr_t lo;
-    uint64_t bytes, elem;
-};
-bool meet(const Range &a, const Range &b) { return a.lo && b.lo && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes; }
-
-uint64_t rows_bytes(int64_t M, int64_t ld, int32_t W) { return ((uint64_t)(M - 1) * (uint64_t)ld + (uint64_t)W) * 4; }
-
-// alignment and address-space fit of every range; then no output may share a byte with an input or with another output
-int check_ranges(const char *api, int64_t M, const Range *ins, int n_in, const Range *outs, int n_out) {
-    for (int pass = 0; pass < 2; ++pass) {
-        const Range *r = pass ? outs : ins;
-        for (int i = 0; i < (pass ? n_out : n_in); ++i) {
-            if (r[i].lo & (r[i].elem - 1))
-                return bad("%s: %s pointer %p is not %llu-byte aligned", api, r[i].name, (void *)r[i].lo, (unsigned long long)r[i].elem);
-            if (r[i].lo && r[i].bytes > UINTPTR_MAX - r[i].lo)
-                return bad("%s: %s at %p with M = %lld does not fit the address space", api, r[i].name, (void *)r[i].lo, (long long)M);
-        }
-    }
-    for (int i = 0; i < n_out; ++i) {
-        for (int j = 0; j < n_in; ++j)
-            if (meet(outs[i], ins[j])) return bad("%s: output %s overlaps the %s", api, outs[i].name, ins[j].name);
-        for (int j = i + 1; j < n_out; ++j)
-            if (meet(outs[i], outs[j])) return bad("%s: outputs %s and %s overlap", api, outs[i].name, outs[j].name);
-    }
-    return MXV_OK;
-}
-
-int check_cat(const char *api, int64_t M, int32_t A, const float *logits, int64_t ld, const void *actions) {
-    if (!logits) return bad("%s: logits pointer is NULL", api);
-    if (!actions) return bad("%s: actions pointer is NULL", api);
-    if (M < 1) return bad("%s: M = %lld must be at least 1", api, (long long)M);
-    if (A < 1 || A > kMaxActions) return bad("%s: A = %d must be in 1..%d", api, (int)A, kMaxActions);
-    if (ld < A) return bad("%s: row stride ld = %lld must be at least A = %d", api, (long long)ld, (int)A);
-    if (ld > kMaxElems / M) return bad("%s: M * ld = %lld * %lld is beyond 2^40 elements", api, (long long)M, (long long)ld);
-    return MXV_OK;
-}
-
-int check_gauss(const char *api, int64_t M, int32_t D, const float *mean, int64_t mean_ld, const float *log_std, int64_t log_std_ld,
-                const float *actions, int64_t actions_ld) {
-    if (!mean) return bad("%s: mean pointer is NULL", api);
-    if (!log_std) return bad("%s: log_std pointer is NULL", api);
-    if (!actions) return bad("%s: actions pointer is NULL", api);
-    if (M < 1) return bad("%s: M = %lld must be at least 1", api, (long long)M);
-    if (D < 1 || D > kMaxDim) return bad("%s: D = %d must be in 1..%d", api, (int)D, kMaxDim);
-    if (mean_ld < D) return bad("%s: row stride mean_ld = %lld must be at least D = %d", api, (long long)mean_ld, (int)D);
-    if (log_std_ld != 0 && log_std_ld < D)
-        return bad("%s: row stride log_std_ld = %lld must be 0 (one shared row) or at least D = %d", api, (long long)log_std_ld, (int)D);
-    if (actions_ld < D) return bad("%s: row stride actions_ld = %lld must be at least D = %d", api, (long long)actions_ld, (int)D);
-    for (const int64_t ld : {mean_ld, log_std_ld, actions_ld})
-        if (ld > kMaxElems / M) return bad("%s: M * ld = %lld * %lld is beyond 2^40 elements", api, (long long)M, (long long)ld);
-    return MXV_OK;
-}
-
-dim3 grid_of(int64_t tiles) { return dim3((unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks)); }
-
-template <typename Args>
-int launch(const char *api, const void *kernel, Args &a, void *stream) {
-    void *args[] = {&a};
-    // hipLaunchKernel returns THIS launch's status (hipGetLastError would also report, and clear, an earlier call's error)
-    const hipError_t e = hipLaunchKernel(kernel, grid_of(a.tiles), dim3(kThreads), args, 0, (hipStream_t)stream);
-    if (e != hipSuccess) return mxv::fail<EvalCall>(nullptr, MXV_ERR_HIP, "%s: kernel launch: %s", api, hipGetErrorString(e));
-    return MXV_OK;
-}
-
+// ---- host: which instantiation ----
 template <template <int> class K>
 const void *pick_cat(int32_t A) {
     switch (A) {
@@ -446,81 +321,81 @@ extern "C" {
 
 int mxv_policy_eval_categorical(void *stream, int64_t M, int32_t A, const float *logits_dev, int64_t ld, const void *actions_dev,
                                 int32_t actions_are_i64, float *log_prob_dev, float *entropy_dev) {
-    const char *api = "mxv_policy_eval_categorical";
-    if (int rc = check_cat(api, M, A, logits_dev, ld, actions_dev)) return rc;
+    const Call<mxv::EvalCall> call{"mxv_policy_eval_categorical", 'M'};
+    if (int rc = call.check_cat(M, A, logits_dev, ld, actions_dev)) return rc;
     const uint64_t ab = actions_are_i64 ? 8 : 4;
     const Range ins[] = {{"logits", (uintptr_t)logits_dev, rows_bytes(M, ld, A), 4}, {"actions", (uintptr_t)actions_dev, (uint64_t)M * ab, ab}};
     const Range outs[] = {{"log_prob", (uintptr_t)log_prob_dev, (uint64_t)M * 4, 4}, {"entropy", (uintptr_t)entropy_dev, (uint64_t)M * 4, 4}};
-    if (int rc = check_ranges(api, M, ins, 2, outs, 2)) return rc;
+    if (int rc = call.check_ranges(M, ins, 2, outs, 2)) return rc;
     CatArgs a{};
     a.logits = logits_dev; a.actions = actions_dev; a.log_prob = log_prob_dev; a.entropy = entropy_dev;
     a.M = M; a.ld = ld; a.tiles = (M + kThreads - 1) / kThreads; a.A = A; a.i64 = actions_are_i64 ? 1 : 0;
-    return launch(api, pick_cat<CatFwd>(A), a, stream);
+    return call.launch(pick_cat<CatFwd>(A), a, stream);
 }
 
 int mxv_policy_eval_categorical_backward(void *stream, int64_t M, int32_t A, const float *logits_dev, int64_t ld, const void *actions_dev,
                                          int32_t actions_are_i64, const float *grad_log_prob_dev, const float *grad_entropy_dev,
                                          float *grad_logits_dev, int64_t grad_ld) {
-    const char *api = "mxv_policy_eval_categorical_backward";
-    if (int rc = check_cat(api, M, A, logits_dev, ld, actions_dev)) return rc;
-    if (!grad_logits_dev) return bad("%s: grad_logits pointer is NULL", api);
-    if (!grad_log_prob_dev && !grad_entropy_dev) return bad("%s: grad_log_prob and grad_entropy are both NULL: there is nothing to propagate", api);
-    if (grad_ld < A) return bad("%s: row stride grad_ld = %lld must be at least A = %d", api, (long long)grad_ld, (int)A);
-    if (grad_ld > kMaxElems / M) return bad("%s: M * ld = %lld * %lld is beyond 2^40 elements", api, (long long)M, (long long)grad_ld);
+    const Call<mxv::EvalCall> call{"mxv_policy_eval_categorical_backward", 'M'};
+    if (int rc = call.check_cat(M, A, logits_dev, ld, actions_dev)) return rc;
+    if (!grad_logits_dev) return call.bad("%s: grad_logits pointer is NULL", call.api);
+    if (!grad_log_prob_dev && !grad_entropy_dev) return call.bad("%s: grad_log_prob and grad_entropy are both NULL: there is nothing to propagate", call.api);
+    if (grad_ld < A) return call.bad("%s: row stride grad_ld = %lld must be at least A = %d", call.api, (long long)grad_ld, (int)A);
+    if (int rc = call.check_stride(grad_ld, M)) return rc;
     const uint64_t ab = actions_are_i64 ? 8 : 4;
     const Range ins[] = {{"logits", (uintptr_t)logits_dev, rows_bytes(M, ld, A), 4}, {"actions", (uintptr_t)actions_dev, (uint64_t)M * ab, ab},
                          {"grad_log_prob", (uintptr_t)grad_log_prob_dev, (uint64_t)M * 4, 4}, {"grad_entropy", (uintptr_t)grad_entropy_dev, (uint64_t)M * 4, 4}};
     const Range outs[] = {{"grad_logits", (uintptr_t)grad_logits_dev, rows_bytes(M, grad_ld, A), 4}};
-    if (int rc = check_ranges(api, M, ins, 4, outs, 1)) return rc;
+    if (int rc = call.check_ranges(M, ins, 4, outs, 1)) return rc;
     CatArgs a{};
     a.logits = logits_dev; a.actions = actions_dev; a.gl = grad_log_prob_dev; a.gh = grad_entropy_dev; a.grad = grad_logits_dev;
     a.M = M; a.ld = ld; a.grad_ld = grad_ld; a.tiles = (M + kThreads - 1) / kThreads; a.A = A; a.i64 = actions_are_i64 ? 1 : 0;
-    return launch(api, pick_cat<CatBwd>(A), a, stream);
+    return call.launch(pick_cat<CatBwd>(A), a, stream);
 }
 
 int mxv_policy_eval_gaussian(void *stream, int64_t M, int32_t D, const float *mean_dev, int64_t mean_ld, const float *log_std_dev,
                              int64_t log_std_ld, const float *actions_dev, int64_t actions_ld, float *log_prob_dev, float *entropy_dev) {
-    const char *api = "mxv_policy_eval_gaussian";
-    if (int rc = check_gauss(api, M, D, mean_dev, mean_ld, log_std_dev, log_std_ld, actions_dev, actions_ld)) return rc;
+    const Call<mxv::EvalCall> call{"mxv_policy_eval_gaussian", 'M'};
+    if (int rc = call.check_gauss(M, D, mean_dev, mean_ld, log_std_dev, log_std_ld, actions_dev, actions_ld)) return rc;
     const Range ins[] = {{"mean", (uintptr_t)mean_dev, rows_bytes(M, mean_ld, D), 4}, {"log_std", (uintptr_t)log_std_dev, rows_bytes(M, log_std_ld, D), 4},
                          {"actions", (uintptr_t)actions_dev, rows_bytes(M, actions_ld, D), 4}};
     const Range outs[] = {{"log_prob", (uintptr_t)log_prob_dev, (uint64_t)M * 4, 4}, {"entropy", (uintptr_t)entropy_dev, (uint64_t)M * 4, 4}};
-    if (int rc = check_ranges(api, M, ins, 3, outs, 2)) return rc;
+    if (int rc = call.check_ranges(M, ins, 3, outs, 2)) return rc;
     GaussArgs a{};
     a.mean = mean_dev; a.log_std = log_std_dev; a.actions = actions_dev; a.log_prob = log_prob_dev; a.entropy = entropy_dev;
     a.M = M; a.mean_ld = mean_ld; a.log_std_ld = log_std_ld; a.actions_ld = actions_ld; a.tiles = (M + kThreads - 1) / kThreads;
-    return launch(api, pick_gauss<GaussFwd>(D), a, stream);
+    return call.launch(pick_gauss<GaussFwd>(D), a, stream);
 }
 
 int mxv_policy_eval_gaussian_backward(void *stream, int64_t M, int32_t D, const float *mean_dev, int64_t mean_ld, const float *log_std_dev,
                                       int64_t log_std_ld, const float *actions_dev, int64_t actions_ld, const float *grad_log_prob_dev,
                                       const float *grad_entropy_dev, float *grad_mean_dev, int64_t grad_mean_ld, float *grad_log_std_dev,
                                       int64_t grad_log_std_ld) {
-    const char *api = "mxv_policy_eval_gaussian_backward";
-    if (int rc = check_gauss(api, M, D, mean_dev, mean_ld, log_std_dev, log_std_ld, actions_dev, actions_ld)) return rc;
-    if (!grad_log_prob_dev && !grad_entropy_dev) return bad("%s: grad_log_prob and grad_entropy are both NULL: there is nothing to propagate", api);
+    const Call<mxv::EvalCall> call{"mxv_policy_eval_gaussian_backward", 'M'};
+    if (int rc = call.check_gauss(M, D, mean_dev, mean_ld, log_std_dev, log_std_ld, actions_dev, actions_ld)) return rc;
+    if (!grad_log_prob_dev && !grad_entropy_dev) return call.bad("%s: grad_log_prob and grad_entropy are both NULL: there is nothing to propagate", call.api);
     if (grad_mean_dev && grad_mean_ld < D)
-        return bad("%s: row stride grad_mean_ld = %lld must be at least D = %d", api, (long long)grad_mean_ld, (int)D);
+        return call.bad("%s: row stride grad_mean_ld = %lld must be at least D = %d", call.api, (long long)grad_mean_ld, (int)D);
     if (grad_log_std_dev && grad_log_std_ld < D)
-        return bad("%s: row stride grad_log_std_ld = %lld must be at least D = %d", api, (long long)grad_log_std_ld, (int)D);
+        return call.bad("%s: row stride grad_log_std_ld = %lld must be at least D = %d", call.api, (long long)grad_log_std_ld, (int)D);
     if (!grad_mean_dev) grad_mean_ld = D;      // an absent output has no layout
     if (!grad_log_std_dev) grad_log_std_ld = D;
     for (const int64_t ld : {grad_mean_ld, grad_log_std_ld})
-        if (ld > kMaxElems / M) return bad("%s: M * ld = %lld * %lld is beyond 2^40 elements", api, (long long)M, (long long)ld);
+        if (int rc = call.check_stride(ld, M)) return rc;
     const Range ins[] = {{"mean", (uintptr_t)mean_dev, rows_bytes(M, mean_ld, D), 4}, {"log_std", (uintptr_t)log_std_dev, rows_bytes(M, log_std_ld, D), 4},
                          {"actions", (uintptr_t)actions_dev, rows_bytes(M, actions_ld, D), 4},
                          {"grad_log_prob", (uintptr_t)grad_log_prob_dev, (uint64_t)M * 4, 4}, {"grad_entropy", (uintptr_t)grad_entropy_dev, (uint64_t)M * 4, 4}};
     const Range outs[] = {{"grad_mean", (uintptr_t)grad_mean_dev, rows_bytes(M, grad_mean_ld, D), 4},
                           {"grad_log_std", (uintptr_t)grad_log_std_dev, rows_bytes(M, grad_log_std_ld, D), 4}};
-    if (int rc = check_ranges(api, M, ins, 5, outs, 2)) return rc;
+    if (int rc = call.check_ranges(M, ins, 5, outs, 2)) return rc;
     GaussArgs a{};
     a.mean = mean_dev; a.log_std = log_std_dev; a.actions = actions_dev; a.gl = grad_log_prob_dev; a.gh = grad_entropy_dev;
     a.grad_mean = grad_mean_dev; a.grad_log_std = grad_log_std_dev;
     a.M = M; a.mean_ld = mean_ld; a.log_std_ld = log_std_ld; a.actions_ld = actions_ld; a.grad_mean_ld = grad_mean_ld;
     a.grad_log_std_ld = grad_log_std_ld; a.tiles = (M + kThreads - 1) / kThreads;
-    return launch(api, pick_gauss<GaussBwd>(D), a, stream);
+    return call.launch(pick_gauss<GaussBwd>(D), a, stream);
 }
 
-const char *mxv_policy_eval_last_error(void) { return mxv::last_error<EvalCall>(nullptr); }
+const char *mxv_policy_eval_last_error(void) { return mxv::last_error<mxv::EvalCall>(nullptr); }
 
 }  // extern "C"

@@ -16,13 +16,11 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native
+from ._policy_args import MAX_ACTION_DIM, MAX_ACTIONS, STRAIGHT_LINE_ACTIONS      # noqa: F401  (the heads' limits: part of this module's surface)
+from ._policy_args import _check as _raise
+from ._policy_args import _index, _ld, _log_std, _one_device, _ptr, _rows, _Sampler, _step, _vector
 
 POLICY_EXPORTS = ("mxv_policy_sample_categorical", "mxv_policy_sample_gaussian", "mxv_policy_last_error", "mxv_policy_last_launch")
-MAX_ACTIONS = 64
-MAX_ACTION_DIM = 4                      # dims of a Gaussian head: one Philox call per env yields four normals
-STRAIGHT_LINE_ACTIONS = (2, 3, 4, 6)    # action counts with a register-resident instantiation (gym_amd/csrc/mxv_policy.hip)
-_U64 = (1 << 64) - 1
-
 lib = _native.lib
 lib.mxv_policy_sample_categorical.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64,
                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -37,12 +35,7 @@ lib.mxv_policy_last_launch.restype = C.c_int
 
 
 def _check(rc: int):
-    if rc == _native.OK:
-        return
-    msg = lib.mxv_policy_last_error().decode()
-    if rc == _native.ERR_INVALID_ARG:
-        raise ValueError(msg)
-    raise _native.MxvError(rc, msg)
+    _raise(rc, lib.mxv_policy_last_error)
 
 
 def last_launch():
@@ -50,46 +43,6 @@ def last_launch():
     v, a, g = C.c_int32(), C.c_int32(), C.c_uint32()
     _check(lib.mxv_policy_last_launch(C.byref(v), C.byref(a), C.byref(g)))
     return v.value, a.value, g.value
-
-
-def _index(name, v):
-    """A non-negative integer below 2^64 as a Python int: int and NumPy integers; not bool, not float, not text."""
-    ok = not isinstance(v, (bool, float, str, bytes))
-    if ok:
-        try:
-            i = int(v)
-            ok = i == v
-        except (TypeError, ValueError):
-            ok = False
-    if not ok or not 0 <= i <= _U64:
-        raise ValueError(f"{name} must be an integer in [0, 2^64), got {v!r}")
-    return i
-
-
-def _logits(t, x):
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"logits must be a torch tensor, got {type(x).__name__}")
-    if x.dtype != t.float32:
-        raise ValueError(f"logits must be torch.float32, got {x.dtype}")
-    if x.dim() != 2 or x.shape[0] < 1 or not 1 <= x.shape[1] <= MAX_ACTIONS:
-        raise ValueError(f"logits must have shape [N, A] with N >= 1 and 1 <= A <= {MAX_ACTIONS}, got {tuple(x.shape)}")
-    if x.shape[1] > 1 and x.stride(1) != 1:
-        raise ValueError(f"logits must be contiguous in their last dimension (stride {x.stride(1)}): rows may be strided views, elements not")
-    if x.shape[0] > 1 and x.stride(0) < x.shape[1]:
-        raise ValueError(f"logits have row stride {x.stride(0)} < A = {x.shape[1]}: rows overlap")
-    return x
-
-
-def _vector(t, x, name, n, dtypes):
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor or None, got {type(x).__name__}")
-    if x.dtype not in dtypes:
-        raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
-    if tuple(x.shape) != (n,):
-        raise ValueError(f"{name} must have shape ({n},), got {tuple(x.shape)}")
-    if n > 1 and x.stride(0) != 1:
-        raise ValueError(f"{name} must be contiguous (stride {x.stride(0)})")
-    return x
 
 
 def sample_categorical(logits, *, seed, step, env_offset=0, action_dtype=None, out=None):
@@ -105,15 +58,9 @@ def sample_categorical(logits, *, seed, step, env_offset=0, action_dtype=None, o
     import torch as t
 
     seed, env_offset = _index("seed", seed), _index("env_offset", env_offset)
-    x = _logits(t, logits)
+    x = _rows(t, logits, "logits", MAX_ACTIONS, f"[N, A] with N >= 1 and 1 <= A <= {MAX_ACTIONS}", two_d=True)
     N, A = x.shape
-    step_t = None
-    if isinstance(step, t.Tensor):
-        if step.dtype != t.int64 or step.numel() != 1:
-            raise ValueError(f"a step tensor must be torch.int64 with one element, got {step.dtype} {tuple(step.shape)}")
-        step_t, step = step, 0
-    else:
-        step = _index("step", step)
+    step, step_t = _step(t, step)
     if action_dtype is None:
         action_dtype = out[0].dtype if out is not None and isinstance(out[0], t.Tensor) else t.int64
     if action_dtype not in (t.int64, t.int32):
@@ -122,56 +69,37 @@ def sample_categorical(logits, *, seed, step, env_offset=0, action_dtype=None, o
         out = tuple(out)
         if len(out) != 3:
             raise ValueError(f"out must hold 3 entries (actions, log_prob, entropy), got {len(out)}")
-        act = _vector(t, out[0], "out (actions)", N, (action_dtype,))
-        lp = None if out[1] is None else _vector(t, out[1], "out (log_prob)", N, (t.float32,))
-        en = None if out[2] is None else _vector(t, out[2], "out (entropy)", N, (t.float32,))
-    dev = x.device
-    for name, y in (("logits", x), ("step", step_t)) + ((("out (actions)", act), ("out (log_prob)", lp), ("out (entropy)", en)) if out is not None else ()):
-        if y is None:
-            continue
-        if not y.is_cuda:
-            raise ValueError(f"{name} must be a device tensor, got one on {y.device} (gym_amd has no CPU fallback)")
-        if y.device != dev:
-            raise ValueError(f"{name} is on {y.device}, logits on {dev}: all tensors must be on one device")
+        act = _vector(t, out[0], "out (actions)", (N,), (action_dtype,))
+        lp = None if out[1] is None else _vector(t, out[1], "out (log_prob)", (N,), (t.float32,))
+        en = None if out[2] is None else _vector(t, out[2], "out (entropy)", (N,), (t.float32,))
+    dev = _one_device((("logits", x), ("step", step_t)) + ((("out (actions)", act), ("out (log_prob)", lp), ("out (entropy)", en)) if out is not None else ()))
     if out is None:
         act = t.empty(N, dtype=action_dtype, device=dev)
         lp = t.empty(N, dtype=t.float32, device=dev)
         en = t.empty(N, dtype=t.float32, device=dev)
-    ld = x.stride(0) if N > 1 else A
     with t.cuda.device(dev):
-        _check(lib.mxv_policy_sample_categorical(t.cuda.current_stream(dev).cuda_stream, N, A, x.data_ptr(), ld, seed, env_offset, step,
-                                                 None if step_t is None else step_t.data_ptr(), act.data_ptr(), int(action_dtype == t.int64),
-                                                 None if lp is None else lp.data_ptr(), None if en is None else en.data_ptr()))
-    return act, lp, en
+        _check(lib.mxv_policy_sample_categorical(t.cuda.current_stream(dev).cuda_stream, N, A, x.data_ptr(), _ld(x, A), seed, env_offset, step,
+                                                 _ptr(step_t), act.data_ptr(), int(action_dtype == t.int64), _ptr(lp), _ptr(en)))
+    return (act, lp, en) if out is None else out      # the caller's own tensors
 
 
-class PolicySampler:
+class PolicySampler(_Sampler):
     """sample_categorical() with the step counter kept on the device: every sample() draws step t of the stream (seed, env_offset) and
     advances t by one on the stream, so that calls recorded into a graph continue the stream at every replay.  state_dict() /
     load_state_dict() carry (seed, env_offset, step): a restored sampler continues bit-identically."""
 
-    def __init__(self, num_actions: int, *, seed: int = 0, env_offset: int = 0, action_dtype=None, device=0):
-        import torch as t
+    _WIDTH = ("num_actions", MAX_ACTIONS)
 
-        if isinstance(num_actions, bool) or not isinstance(num_actions, int) or not 1 <= num_actions <= MAX_ACTIONS:
-            raise ValueError(f"num_actions must be an integer in 1..{MAX_ACTIONS}, got {num_actions!r}")
-        action_dtype = t.int64 if action_dtype is None else action_dtype
-        if action_dtype not in (t.int64, t.int32):
+    def __init__(self, num_actions: int, *, seed: int = 0, env_offset: int = 0, action_dtype=None, device=0):
+        super().__init__(num_actions, seed=seed, env_offset=env_offset, device=device)
+        t = self._torch
+        self.action_dtype = t.int64 if action_dtype is None else action_dtype
+        if self.action_dtype not in (t.int64, t.int32):
             raise ValueError(f"action_dtype must be torch.int64 or torch.int32, got {action_dtype}")
-        if not t.cuda.is_available():
-            raise RuntimeError("PolicySampler needs a HIP device (torch.cuda.is_available() is False); gym_amd has no CPU fallback")
-        self._torch = t
-        self.num_actions = num_actions
-        self.seed, self.env_offset = _index("seed", seed), _index("env_offset", env_offset)
-        self.action_dtype = action_dtype
-        self.device = device if isinstance(device, t.device) else t.device("cuda", device)
-        self._step = t.zeros(1, dtype=t.int64, device=self.device)
-        t.cuda.current_stream(self.device).synchronize()     # construction is rare: the counter is ready on whichever stream samples
 
     def sample(self, logits, out=None):
         """-> (actions, log_prob, entropy) of the next step of the stream; arguments as sample_categorical()."""
-        if isinstance(logits, self._torch.Tensor) and logits.dim() == 2 and logits.shape[1] != self.num_actions:
-            raise ValueError(f"logits must have {self.num_actions} columns (num_actions), got {tuple(logits.shape)}")
+        self._columns("logits", logits, leading_dims=False)
         return sample_categorical(logits, seed=self.seed, step=self._step, env_offset=self.env_offset, action_dtype=self.action_dtype,
                                   out=out)
 
@@ -180,38 +108,8 @@ class PolicySampler:
         nothing and leaves the stream where it is."""
         from .policy_eval import evaluate_categorical
 
-        if isinstance(logits, self._torch.Tensor) and logits.dim() >= 2 and logits.shape[-1] != self.num_actions:
-            raise ValueError(f"logits must have {self.num_actions} columns (num_actions), got {tuple(logits.shape)}")
+        self._columns("logits", logits, leading_dims=True)
         return evaluate_categorical(logits, actions, out=out)
-
-    def step_index(self) -> int:
-        """How many draws the stream has made (synchronises)."""
-        return int(self._step.item()) & _U64
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "env_offset": self.env_offset, "step": self.step_index(), "num_actions": self.num_actions}
-
-    def load_state_dict(self, state: dict):
-        if int(state.get("num_actions", self.num_actions)) != self.num_actions:
-            raise ValueError(f"the state is of a sampler with {state['num_actions']} actions, this one has {self.num_actions}")
-        self.seed, self.env_offset = _index("seed", state["seed"]), _index("env_offset", state["env_offset"])
-        step = _index("step", state["step"])
-        self._step.fill_(step - (1 << 64) if step >= (1 << 63) else step)
-
-
-def _rows(t, x, name, max_cols, what):
-    """A float32 [N, D] tensor whose rows may be strided views, elements not."""
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype != t.float32:
-        raise ValueError(f"{name} must be torch.float32, got {x.dtype}")
-    if x.dim() != 2 or x.shape[0] < 1 or not 1 <= x.shape[1] <= max_cols:
-        raise ValueError(f"{name} must have shape {what}, got {tuple(x.shape)}")
-    if x.shape[1] > 1 and x.stride(1) != 1:
-        raise ValueError(f"{name} must be contiguous in its last dimension (stride {x.stride(1)}): rows may be strided views, elements not")
-    if x.shape[0] > 1 and x.stride(0) < x.shape[1]:
-        raise ValueError(f"{name} has row stride {x.stride(0)} < D = {x.shape[1]}: rows overlap")
-    return x
 
 
 def sample_gaussian(mean, log_std, *, seed, step, env_offset=0, out=None):
@@ -228,82 +126,44 @@ def sample_gaussian(mean, log_std, *, seed, step, env_offset=0, out=None):
     import torch as t
 
     seed, env_offset = _index("seed", seed), _index("env_offset", env_offset)
-    mu = _rows(t, mean, "mean", MAX_ACTION_DIM, f"[N, D] with N >= 1 and 1 <= D <= {MAX_ACTION_DIM}")
+    mu = _rows(t, mean, "mean", MAX_ACTION_DIM, f"[N, D] with N >= 1 and 1 <= D <= {MAX_ACTION_DIM}", two_d=True)
     N, D = mu.shape
-    if not isinstance(log_std, t.Tensor):
-        raise ValueError(f"log_std must be a torch tensor, got {type(log_std).__name__}")
-    if log_std.dim() == 1:
-        if log_std.dtype != t.float32:
-            raise ValueError(f"log_std must be torch.float32, got {log_std.dtype}")
-        if log_std.shape[0] != D:
-            raise ValueError(f"log_std must have shape ({N}, {D}) or ({D},), got {tuple(log_std.shape)}")
-        if D > 1 and log_std.stride(0) != 1:
-            raise ValueError(f"log_std must be contiguous in its last dimension (stride {log_std.stride(0)})")
-        ls, ls_ld = log_std, 0
-    else:
-        ls = _rows(t, log_std, "log_std", MAX_ACTION_DIM, f"({N}, {D}) or ({D},)")
-        if tuple(ls.shape) != (N, D):
-            raise ValueError(f"log_std must have shape ({N}, {D}) or ({D},), got {tuple(ls.shape)}")
-        ls_ld = ls.stride(0) if N > 1 else D
-    step_t = None
-    if isinstance(step, t.Tensor):
-        if step.dtype != t.int64 or step.numel() != 1:
-            raise ValueError(f"a step tensor must be torch.int64 with one element, got {step.dtype} {tuple(step.shape)}")
-        step_t, step = step, 0
-    else:
-        step = _index("step", step)
+    ls, ls_ld = _log_std(t, log_std, mu, two_d=True)
+    step, step_t = _step(t, step)
     if out is not None:
         out = tuple(out)
         if len(out) != 3:
             raise ValueError(f"out must hold 3 entries (actions, log_prob, entropy), got {len(out)}")
-        act = _rows(t, out[0], "out (actions)", MAX_ACTION_DIM, f"({N}, {D})")
+        act = _rows(t, out[0], "out (actions)", MAX_ACTION_DIM, f"({N}, {D})", two_d=True)
         if tuple(act.shape) != (N, D):
             raise ValueError(f"out (actions) must have shape ({N}, {D}), got {tuple(act.shape)}")
-        lp = None if out[1] is None else _vector(t, out[1], "out (log_prob)", N, (t.float32,))
-        en = None if out[2] is None else _vector(t, out[2], "out (entropy)", N, (t.float32,))
-    dev = mu.device
-    for name, y in (("mean", mu), ("log_std", ls), ("step", step_t)) + ((("out (actions)", act), ("out (log_prob)", lp), ("out (entropy)", en)) if out is not None else ()):
-        if y is None:
-            continue
-        if not y.is_cuda:
-            raise ValueError(f"{name} must be a device tensor, got one on {y.device} (gym_amd has no CPU fallback)")
-        if y.device != dev:
-            raise ValueError(f"{name} is on {y.device}, mean on {dev}: all tensors must be on one device")
+        lp = None if out[1] is None else _vector(t, out[1], "out (log_prob)", (N,), (t.float32,))
+        en = None if out[2] is None else _vector(t, out[2], "out (entropy)", (N,), (t.float32,))
+    dev = _one_device((("mean", mu), ("log_std", ls), ("step", step_t))
+                      + ((("out (actions)", act), ("out (log_prob)", lp), ("out (entropy)", en)) if out is not None else ()))
     if out is None:
         act = t.empty((N, D), dtype=t.float32, device=dev)
         lp = t.empty(N, dtype=t.float32, device=dev)
         en = t.empty(N, dtype=t.float32, device=dev)
     with t.cuda.device(dev):
-        _check(lib.mxv_policy_sample_gaussian(t.cuda.current_stream(dev).cuda_stream, N, D, mu.data_ptr(), mu.stride(0) if N > 1 else D,
-                                              ls.data_ptr(), ls_ld, seed, env_offset, step, None if step_t is None else step_t.data_ptr(),
-                                              act.data_ptr(), act.stride(0) if N > 1 else D, None if lp is None else lp.data_ptr(),
-                                              None if en is None else en.data_ptr()))
-    return act, lp, en
+        _check(lib.mxv_policy_sample_gaussian(t.cuda.current_stream(dev).cuda_stream, N, D, mu.data_ptr(), _ld(mu, D), ls.data_ptr(), ls_ld, seed,
+                                              env_offset, step, _ptr(step_t), act.data_ptr(), _ld(act, D), _ptr(lp), _ptr(en)))
+    return (act, lp, en) if out is None else out      # the caller's own tensors
 
 
-class GaussianSampler:
+class GaussianSampler(_Sampler):
     """sample_gaussian() with the step counter kept on the device: every sample() draws step t of the stream (seed, env_offset) and advances
     t by one on the stream, so that calls recorded into a graph continue the stream at every replay.  state_dict() / load_state_dict()
     carry (seed, env_offset, step): a restored sampler continues bit-identically."""
 
-    def __init__(self, action_dim: int, *, seed: int = 0, env_offset: int = 0, device=0):
-        if isinstance(action_dim, bool) or not isinstance(action_dim, int) or not 1 <= action_dim <= MAX_ACTION_DIM:
-            raise ValueError(f"action_dim must be an integer in 1..{MAX_ACTION_DIM}, got {action_dim!r}")
-        import torch as t
+    _WIDTH = ("action_dim", MAX_ACTION_DIM)
 
-        if not t.cuda.is_available():
-            raise RuntimeError("GaussianSampler needs a HIP device (torch.cuda.is_available() is False); gym_amd has no CPU fallback")
-        self._torch = t
-        self.action_dim = action_dim
-        self.seed, self.env_offset = _index("seed", seed), _index("env_offset", env_offset)
-        self.device = device if isinstance(device, t.device) else t.device("cuda", device)
-        self._step = t.zeros(1, dtype=t.int64, device=self.device)
-        t.cuda.current_stream(self.device).synchronize()     # construction is rare: the counter is ready on whichever stream samples
+    def __init__(self, action_dim: int, *, seed: int = 0, env_offset: int = 0, device=0):
+        super().__init__(action_dim, seed=seed, env_offset=env_offset, device=device)
 
     def sample(self, mean, log_std, out=None):
         """-> (actions, log_prob, entropy) of the next step of the stream; arguments as sample_gaussian()."""
-        if isinstance(mean, self._torch.Tensor) and mean.dim() == 2 and mean.shape[1] != self.action_dim:
-            raise ValueError(f"mean must have {self.action_dim} columns (action_dim), got {tuple(mean.shape)}")
+        self._columns("mean", mean, leading_dims=False)
         return sample_gaussian(mean, log_std, seed=self.seed, step=self._step, env_offset=self.env_offset, out=out)
 
     def evaluate(self, mean, log_std, actions, out=None):
@@ -311,20 +171,5 @@ class GaussianSampler:
         nothing and leaves the stream where it is."""
         from .policy_eval import evaluate_gaussian
 
-        if isinstance(mean, self._torch.Tensor) and mean.dim() >= 2 and mean.shape[-1] != self.action_dim:
-            raise ValueError(f"mean must have {self.action_dim} columns (action_dim), got {tuple(mean.shape)}")
+        self._columns("mean", mean, leading_dims=True)
         return evaluate_gaussian(mean, log_std, actions, out=out)
-
-    def step_index(self) -> int:
-        """How many draws the stream has made (synchronises)."""
-        return int(self._step.item()) & _U64
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "env_offset": self.env_offset, "step": self.step_index(), "action_dim": self.action_dim}
-
-    def load_state_dict(self, state: dict):
-        if int(state.get("action_dim", self.action_dim)) != self.action_dim:
-            raise ValueError(f"the state is of a sampler with action_dim {state['action_dim']}, this one has {self.action_dim}")
-        self.seed, self.env_offset = _index("seed", state["seed"]), _index("env_offset", state["env_offset"])
-        step = _index("step", state["step"])
-        self._step.fill_(step - (1 << 64) if step >= (1 << 63) else step)

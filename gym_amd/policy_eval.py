@@ -18,7 +18,9 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native
-from .policy import MAX_ACTION_DIM, MAX_ACTIONS, STRAIGHT_LINE_ACTIONS      # the samplers' limits and register-resident action counts
+from ._policy_args import MAX_ACTION_DIM, MAX_ACTIONS, STRAIGHT_LINE_ACTIONS      # noqa: F401  (the heads' limits: part of this module's surface)
+from ._policy_args import _check as _raise
+from ._policy_args import _ld, _log_std, _log_std_ld, _one_device, _ptr, _rows, _vector
 
 EVAL_EXPORTS = ("mxv_policy_eval_categorical", "mxv_policy_eval_categorical_backward", "mxv_policy_eval_gaussian",
                 "mxv_policy_eval_gaussian_backward", "mxv_policy_eval_last_error")
@@ -40,58 +42,7 @@ lib.mxv_policy_eval_last_error.restype = C.c_char_p
 
 
 def _check(rc: int):
-    if rc == _native.OK:
-        return
-    msg = lib.mxv_policy_eval_last_error().decode()
-    if rc == _native.ERR_INVALID_ARG:
-        raise ValueError(msg)
-    raise _native.MxvError(rc, msg)
-
-
-def _ptr(x):
-    return None if x is None else x.data_ptr()
-
-
-def _rows(t, x, name, max_cols, what):
-    """A float32 [..., W] tensor as its [M, W] rows: 2-D tensors may have strided rows (views into wider buffers), more dims must
-    flatten without a copy."""
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype != t.float32:
-        raise ValueError(f"{name} must be torch.float32, got {x.dtype}")
-    if x.dim() < 2 or x.numel() == 0 or not 1 <= x.shape[-1] <= max_cols:
-        raise ValueError(f"{name} must have shape {what}, got {tuple(x.shape)}")
-    W = x.shape[-1]
-    if x.dim() == 2:
-        x2 = x
-    else:
-        try:
-            x2 = x.view(-1, W)
-        except RuntimeError:
-            raise ValueError(f"{name} of shape {tuple(x.shape)} with strides {tuple(x.stride())} cannot be viewed as [M, {W}] rows "
-                             f"(view(-1, {W}) fails): pass a contiguous tensor") from None
-    if W > 1 and x2.stride(1) != 1:
-        raise ValueError(f"{name} must be contiguous in its last dimension (stride {x2.stride(1)}): rows may be strided views, elements not")
-    if x2.shape[0] > 1 and x2.stride(0) < W:
-        raise ValueError(f"{name} has row stride {x2.stride(0)} < {W}: rows overlap")
-    return x2
-
-
-def _vector(t, x, name, lead, dtypes):
-    """A tensor of shape `lead` (the rows' leading dims) as a contiguous [M] vector."""
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype not in dtypes:
-        raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
-    if tuple(x.shape) != tuple(lead):
-        raise ValueError(f"{name} must have shape {tuple(lead)}, got {tuple(x.shape)}")
-    try:
-        v = x.view(-1)
-    except RuntimeError:
-        v = None
-    if v is None or (v.shape[0] > 1 and v.stride(0) != 1):
-        raise ValueError(f"{name} must be contiguous (strides {tuple(x.stride())})")
-    return v
+    _raise(rc, lib.mxv_policy_eval_last_error)
 
 
 def _outputs(t, out, lead, grads):
@@ -102,22 +53,6 @@ def _outputs(t, out, lead, grads):
     if len(out) != 2:
         raise ValueError(f"out must hold 2 entries (log_prob, entropy), got {len(out)}")
     return tuple(None if o is None else _vector(t, o, f"out ({n})", lead, (t.float32,)) for o, n in zip(out, ("log_prob", "entropy")))
-
-
-def _one_device(named, first):
-    dev = named[0][1].device
-    for name, y in named:
-        if y is None:
-            continue
-        if not y.is_cuda:
-            raise ValueError(f"{name} must be a device tensor, got one on {y.device} (gym_amd has no CPU fallback)")
-        if y.device != dev:
-            raise ValueError(f"{name} is on {y.device}, {first} on {dev}: all tensors must be on one device")
-    return dev
-
-
-def _ld(x2, W):
-    return x2.stride(0) if x2.shape[0] > 1 else W
 
 
 def _cat_forward(t, x2, act, lp, en):
@@ -133,7 +68,7 @@ def _gauss_forward(t, mu2, ls, act2, lp, en):
     dev = mu2.device
     with t.cuda.device(dev):
         _check(lib.mxv_policy_eval_gaussian(t.cuda.current_stream(dev).cuda_stream, M, D, mu2.data_ptr(), _ld(mu2, D), ls.data_ptr(),
-                                            0 if ls.dim() == 1 else _ld(ls, D), act2.data_ptr(), _ld(act2, D), _ptr(lp), _ptr(en)))
+                                            _log_std_ld(ls, D), act2.data_ptr(), _ld(act2, D), _ptr(lp), _ptr(en)))
 
 
 def _grad_vector(g):
@@ -204,7 +139,7 @@ def _functions():
             g_ls = t.empty((M, D), dtype=t.float32, device=dev) if need_ls else None
             with t.cuda.device(dev):
                 _check(lib.mxv_policy_eval_gaussian_backward(t.cuda.current_stream(dev).cuda_stream, M, D, mu2.data_ptr(), _ld(mu2, D),
-                                                             ls.data_ptr(), 0 if ls.dim() == 1 else _ld(ls, D), act2.data_ptr(), _ld(act2, D),
+                                                             ls.data_ptr(), _log_std_ld(ls, D), act2.data_ptr(), _ld(act2, D),
                                                              _ptr(g_lp), _ptr(g_en), _ptr(g_mu), D, _ptr(g_ls), D))
             if need_ls and ls.dim() == 1:
                 g_ls = g_ls.sum(dim=0)      # the shared row's gradient: a torch reduction, outside the bit-defined rule
@@ -233,7 +168,7 @@ def evaluate_categorical(logits, actions, *, out=None):
     lp = en = None
     if out is not None:
         lp, en = _outputs(t, out, lead, grads)
-    _one_device((("logits", x2), ("actions", act), ("out (log_prob)", lp), ("out (entropy)", en)), "logits")
+    _one_device((("logits", x2), ("actions", act), ("out (log_prob)", lp), ("out (entropy)", en)))
     if grads:
         lp, en = _functions()[0].apply(x2, act)
         return lp.view(lead), en.view(lead)
@@ -262,20 +197,7 @@ def evaluate_gaussian(mean, log_std, actions, *, out=None):
     what = f"[..., D] with at least one row and 1 <= D <= {MAX_ACTION_DIM}"
     mu2 = _rows(t, mean, "mean", MAX_ACTION_DIM, what)
     lead, D = mean.shape[:-1], mean.shape[-1]
-    if not isinstance(log_std, t.Tensor):
-        raise ValueError(f"log_std must be a torch tensor, got {type(log_std).__name__}")
-    if log_std.dim() == 1:
-        if log_std.dtype != t.float32:
-            raise ValueError(f"log_std must be torch.float32, got {log_std.dtype}")
-        if log_std.shape[0] != D:
-            raise ValueError(f"log_std must have shape {tuple(mean.shape)} or ({D},), got {tuple(log_std.shape)}")
-        if D > 1 and log_std.stride(0) != 1:
-            raise ValueError(f"log_std must be contiguous in its last dimension (stride {log_std.stride(0)})")
-        ls = log_std
-    else:
-        ls = _rows(t, log_std, "log_std", MAX_ACTION_DIM, f"{tuple(mean.shape)} or ({D},)")
-        if tuple(log_std.shape) != tuple(mean.shape):
-            raise ValueError(f"log_std must have shape {tuple(mean.shape)} or ({D},), got {tuple(log_std.shape)}")
+    ls, _ = _log_std(t, log_std, mean)
     act2 = _rows(t, actions, "actions", MAX_ACTION_DIM, f"{tuple(mean.shape)}")
     if tuple(actions.shape) != tuple(mean.shape):
         raise ValueError(f"actions must have shape {tuple(mean.shape)}, got {tuple(actions.shape)}")
@@ -285,7 +207,7 @@ def evaluate_gaussian(mean, log_std, actions, *, out=None):
     lp = en = None
     if out is not None:
         lp, en = _outputs(t, out, lead, grads)
-    _one_device((("mean", mu2), ("log_std", ls), ("actions", act2), ("out (log_prob)", lp), ("out (entropy)", en)), "mean")
+    _one_device((("mean", mu2), ("log_std", ls), ("actions", act2), ("out (log_prob)", lp), ("out (entropy)", en)))
     if grads:
         lp, en = _functions()[1].apply(mu2, ls, act2)
         return lp.view(lead), en.view(lead)

@@ -26,7 +26,7 @@
  * 0x7FC00000 (as mxv_gae.h fixes it), and no error: the action stays valid for the env, the NaNs tell the learner.
  *
  * EXP and LOG are these operation sequences, not calls into a math library (tools/policy_coefficients.py generates the constants:
- * exact fractions, or ln 2 / 1/ln 2 / sqrt(1/2), rounded once to double; they are listed in gym_amd/csrc/mxv_policy.hip):
+ * exact fractions, or ln 2 / 1/ln 2 / sqrt(1/2), rounded once to double; they are listed in gym_amd/csrc/mxv_policy_rule.hpp):
  *   EXP(d), -708 <= d <= 0:
  *     k = rint(d * inv_ln2)                           (round half to even)
  *     r = (d - k * ln2_hi) - k * ln2_lo               (ln2_hi: the first 32 bits of ln 2, so k * ln2_hi is exact)
@@ -96,7 +96,7 @@ int mxv_policy_sample_categorical(void *stream, int64_t N, int32_t A, const floa
  *     c = 1.0 + z * Q(z),      Q Horner in z with (-1)^j / (2j)!,   j = 10..1:  Q = 1/20!;   Q = Q * z + (-1)^j / (2j)!    for j = 9..1
  *     (sn, cs) by k & 3:   0: (s, c)    1: (c, -s)    2: (-s, -c)    3: (-c, s)
  * Everything is a select; there is no divergent branch in the rule.  tools/gaussian_coefficients.py generates the constants (they are
- * listed in gym_amd/csrc/mxv_gaussian.hip).
+ * listed in gym_amd/csrc/mxv_policy_rule.hpp, the one text that all the kernels of this rule include).
  *
  * Range.  With 32-bit uniforms u >= 2^-33, so |z_j| <= sqrt(2 * 33 ln 2) = 6.7639...: the tails beyond 6.76 sigma (probability 1.4e-11)
  * are not drawn.

@@ -2,13 +2,15 @@
 and log_std, their log-probabilities and the entropy.  Every line below is one IEEE float64 operation on whole columns (NumPy neither
 fuses nor re-associates them), in the order the rule states; LOG, SINCOS2PI and EXP are the header's operation sequences, not libm;
 `/` and sqrt are IEEE.  The device must produce the same bits (tests/test_gpu_gaussian.py), and tests/test_gaussian_host.py holds this
-file to 200-bit mpmath.  The Philox words come from oracle.philox4x32_10, the constants from tools/gaussian_coefficients.py."""
+file to 200-bit mpmath.  The Philox words come from oracle.philox4x32_10, the constants from tools/gaussian_coefficients.py.  What the rule
+shares with the categorical one — EXP, LOG, their constants, u01 and the float32 helpers — is tests/policy_host.py's, under the same names."""
 import os
 import sys
 
 import numpy as np
 
 from conftest import ROOT
+from policy_host import CANONICAL_NAN, EXP, EXP_C, INV_LN2, LN2_HI, LN2_LO, LOG, LOG_C, SQRT_HALF, bits, rule_block, to_f32, u01      # noqa: F401
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 try:
@@ -16,7 +18,6 @@ try:
 finally:
     sys.path.pop(0)
 
-CANONICAL_NAN = np.uint32(0x7FC00000)
 STREAM_GAUSSIAN = 8
 MAX_DIM = 4
 LOG_STD_MAX = 80.0
@@ -40,43 +41,9 @@ def bar(b):
 
 
 _C = _coef.constants()
-INV_LN2, LN2_HI, LN2_LO, SQRT_HALF = (np.float64(_C[k]) for k in ("inv_ln2", "ln2_hi", "ln2_lo", "sqrt_half"))
 PIO2_HI, PIO2_LO, HALF_LOG_2PI, ENT_C = (np.float64(_C[k]) for k in ("pio2_hi", "pio2_lo", "half_log_2pi", "ent_c"))
-EXP_C = [np.float64(x) for x in _C["exp_c"]]
-LOG_C = [np.float64(x) for x in _C["log_c"]]
 SIN_C = [np.float64(x) for x in _C["sin_c"]]
 COS_C = [np.float64(x) for x in _C["cos_c"]]
-TWO_M32 = np.float64(2.0 ** -32)
-
-
-def EXP(d):
-    """|d| <= 80, float64."""
-    d = np.asarray(d, np.float64)
-    k = np.rint(d * INV_LN2)
-    r = (d - k * LN2_HI) - k * LN2_LO
-    p = np.full_like(d, EXP_C[-1])
-    for c in EXP_C[-2::-1]:
-        p = p * r + c
-    return np.ldexp(p, k.astype(np.int32))
-
-
-def LOG(S):
-    """2^-33 <= S < 64, float64."""
-    S = np.asarray(S, np.float64)
-    f, e = np.frexp(S)                        # f in [1/2, 1)
-    low = f < SQRT_HALF
-    f = np.where(low, f * 2.0, f)             # exact: f in [sqrt 1/2, sqrt 2)
-    e = np.where(low, e - 1, e).astype(np.float64)
-    s = (f - 1.0) / (f + 1.0)
-    z = s * s
-    p = np.full_like(S, LOG_C[-1])
-    for c in LOG_C[-2::-1]:
-        p = p * z + c
-    return ((e * LN2_HI) + (2.0 * s) * p) + e * LN2_LO
-
-
-def u01(w):
-    return (np.asarray(w, np.uint32).astype(np.float64) + 0.5) * TWO_M32
 
 
 def sincos_parts(w):
@@ -114,18 +81,6 @@ def normal_pair(wa, wb):
     rad = np.sqrt(-2.0 * LOG(u))
     sn, cs = SINCOS2PI(wb)
     return rad * cs, rad * sn
-
-
-def to_f32(x):
-    with np.errstate(all="ignore"):
-        y = np.asarray(x, np.float64).astype(np.float32)
-    b = y.view(np.uint32).copy()
-    b[np.isnan(y)] = CANONICAL_NAN
-    return b.view(np.float32)
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
 
 
 _words_cache = {}

@@ -4,6 +4,7 @@ the rule states; EXP and LOG are the header's operation sequences, not libm.  Th
 (tests/test_gpu_policy.py), and tests/test_policy_host.py holds this file to 200-bit mpmath.  The Philox words come from
 oracle.philox4x32_10, the constants from tools/policy_coefficients.py."""
 import os
+import re
 import sys
 
 import numpy as np
@@ -30,10 +31,24 @@ _C = _coef.constants()
 INV_LN2, LN2_HI, LN2_LO, SQRT_HALF = (np.float64(_C[k]) for k in ("inv_ln2", "ln2_hi", "ln2_lo", "sqrt_half"))
 EXP_C = [np.float64(x) for x in _C["exp_c"]]
 LOG_C = [np.float64(x) for x in _C["log_c"]]
+# the names of the generated constant block (tools/gaussian_coefficients.py), as a C++ file would define them
+RULE_NAMES = re.compile(r"constexpr double k(InvLn2|Ln2Hi|Ln2Lo|SqrtHalf|ExpC|LogC|Pio2Hi|Pio2Lo|HalfLog2Pi|EntC|SinC|CosC)\b")
+
+
+def rule_block(kernel_file):
+    """The generated constant block of gym_amd/csrc/mxv_policy_rule.hpp, the one text of it: `kernel_file` includes that header and
+    defines none of the block's names itself.  -> (the block, the kernel file's source)"""
+    csrc = os.path.join(ROOT, "gym_amd", "csrc")
+    src = open(os.path.join(csrc, kernel_file)).read()
+    assert '#include "mxv_policy_rule.hpp"' in src and not RULE_NAMES.search(src), kernel_file
+    rule = open(os.path.join(csrc, "mxv_policy_rule.hpp")).read()
+    assert len(RULE_NAMES.findall(rule)) == 12      # each name once
+    block = rule[rule.index("gaussian_coefficients.py, verbatim"):rule.index("end of the generated block")]
+    return "\n".join(block.splitlines()[1:-1]), src
 
 
 def EXP(d):
-    """d in [-708, 0], float64."""
+    """d in [-708, 0] (categorical) or |d| <= 80 (Gaussian, tests/gaussian_host.py), float64."""
     d = np.asarray(d, np.float64)
     k = np.rint(d * INV_LN2)
     r = (d - k * LN2_HI) - k * LN2_LO
@@ -44,7 +59,7 @@ def EXP(d):
 
 
 def LOG(S):
-    """S in [1, 64], float64."""
+    """S in [1, 64] (categorical) or 2^-33 <= S < 1 (Gaussian), float64."""
     S = np.asarray(S, np.float64)
     f, e = np.frexp(S)                        # f in [1/2, 1)
     low = f < SQRT_HALF

@@ -273,9 +273,8 @@ def test_the_kernel_source_carries_the_generated_constants():
         import policy_coefficients
     finally:
         sys.path.pop(0)
-    src = open(os.path.join(ROOT, "gym_amd", "csrc", "mxv_gaussian.hip")).read()
-    block = src[src.index("gaussian_coefficients.py, verbatim"):src.index("end of the generated block")]
-    assert "\n".join(l for l in block.splitlines()[1:-1]) == gaussian_coefficients.block()
+    block, src = gh.rule_block("mxv_gaussian.hip")
+    assert block == gaussian_coefficients.block() and block.startswith(policy_coefficients.block() + "\n")
     # the shared constants are the categorical rule's, value for value
     g, p = gaussian_coefficients.constants(), policy_coefficients.constants()
     assert all(g[k] == p[k] for k in p) and gaussian_coefficients.block().startswith(policy_coefficients.block())

@@ -273,11 +273,11 @@ def test_the_kernel_source_carries_the_generated_constants():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
         import gaussian_coefficients
+        import policy_coefficients
     finally:
         sys.path.pop(0)
-    src = open(os.path.join(ROOT, "gym_amd", "csrc", "mxv_policy_eval.hip")).read()
-    block = src[src.index("gaussian_coefficients.py, verbatim"):src.index("end of the generated block")]
-    assert "\n".join(l for l in block.splitlines()[1:-1]) == gaussian_coefficients.block()
+    block, _ = ph.rule_block("mxv_policy_eval.hip")
+    assert block == gaussian_coefficients.block() and block.startswith(policy_coefficients.block() + "\n")
     for script in ("build.sh", "build_asan.sh"):
         assert "mxv_policy_eval.hip" in open(os.path.join(ROOT, "gym_amd", "csrc", script)).read(), script
 

@@ -187,12 +187,12 @@ def test_masks_extremes_and_degenerate_rows():
 def test_the_kernel_source_carries_the_generated_constants():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
+        import gaussian_coefficients
         import policy_coefficients
     finally:
         sys.path.pop(0)
-    src = open(os.path.join(ROOT, "gym_amd", "csrc", "mxv_policy.hip")).read()
-    block = src[src.index("policy_coefficients.py, verbatim"):src.index("end of the generated block")]
-    assert "\n".join(l for l in block.splitlines()[1:-1]) == policy_coefficients.block()
+    block, src = ph.rule_block("mxv_policy.hip")
+    assert block == gaussian_coefficients.block() and block.startswith(policy_coefficients.block() + "\n")
     tag = re.search(r"kStreamPolicy = (\d+)u", src)
     assert tag and int(tag.group(1)) == ph.STREAM_POLICY == 7
     assert "7<<28" in open(os.path.join(ROOT, "include", "mxv.h")).read().replace(" ", "")

@@ -2,8 +2,8 @@
 """The constants of the Gaussian rule in include/mxv_policy.h, generated: every one is an exact fraction — or pi/2,
 ln(2 pi), ln 2, 1/ln 2, sqrt(1/2) from arithmetic of 250 decimal digits (more than 800 bits) — rounded once, to nearest even, to
 double.  ln2_hi / ln2_lo / inv_ln2 / sqrt_half and the EXP / LOG coefficients are those of tools/policy_coefficients.py.  Prints the
-C++ block that gym_amd/csrc/mxv_gaussian.hip carries verbatim (tests/test_gaussian_host.py compares the two and the NumPy twin against
-this module).
+C++ block that gym_amd/csrc/mxv_policy_rule.hpp carries verbatim, once, for every kernel of the policy heads (tests/test_gaussian_host.py
+compares the two and the NumPy twin against this module).
 
     python tools/gaussian_coefficients.py          # the block
 """

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The constants of EXP and LOG in include/mxv_policy.h, generated: every one is an exact fraction — or ln 2 / 1/ln 2 /
-sqrt(1/2) from 200-digit integer arithmetic — rounded once, to nearest even, to double.  Prints the C++ block that
-gym_amd/csrc/mxv_policy.hip carries verbatim (tests/test_policy_host.py compares the two and the NumPy twin against this module).
+sqrt(1/2) from 200-digit integer arithmetic — rounded once, to nearest even, to double.  Prints the first lines of the C++ block that
+gym_amd/csrc/mxv_policy_rule.hpp carries verbatim (the whole block is tools/gaussian_coefficients.py's; tests/test_policy_host.py compares
+the two and the NumPy twin against this module).
 
     python tools/policy_coefficients.py            # the block
 """
