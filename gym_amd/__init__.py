@@ -36,6 +36,8 @@ _LAZY = {
     "GaussianSampler": ("gym_amd.policy", "GaussianSampler"),
     "evaluate_categorical": ("gym_amd.policy_eval", "evaluate_categorical"),
     "evaluate_gaussian": ("gym_amd.policy_eval", "evaluate_gaussian"),
+    "advantage_moments": ("gym_amd.ppo", "advantage_moments"),
+    "ppo_clip_loss": ("gym_amd.ppo", "ppo_clip_loss"),
 }
 
 

@@ -1,7 +1,7 @@
 // mxv_policy_host.hpp — the host side that the handle-free policy calls share (include/mxv_policy.h, include/mxv_policy_eval.h): their
 // error slots, the argument checks that run before the device is touched, and the launch.  mxv_policy.hip, mxv_gaussian.hip and
 // mxv_policy_eval.hip keep only what is their own: the ranges of their arguments, filling the kernel's struct and choosing the
-// instantiation.  Host code only: no kernels here.
+// instantiation.  mxv_ppo.hip (include/mxv_ppo.h) uses the same Call with its own slot.  Host code only: no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,9 @@ struct PolicyCall {   // include/mxv_policy.h
     std::string error;
 };
 struct EvalCall {   // include/mxv_policy_eval.h: mxv_policy_eval_last_error
+    std::string error;
+};
+struct PpoCall {   // include/mxv_ppo.h: mxv_ppo_last_error
     std::string error;
 };
 
@@ -109,6 +112,14 @@ struct Call {
         void *args[] = {&a};
         // hipLaunchKernel returns THIS launch's status (hipGetLastError would also report, and clear, an earlier call's error)
         const hipError_t e = hipLaunchKernel(kernel, grid_of(a.tiles), dim3(rule::kThreads), args, 0, (hipStream_t)stream);
+        return e == hipSuccess ? MXV_OK : hip_failed("kernel launch", e);
+    }
+
+    // `kernel`(a) on `stream` with one workgroup per leaf of a sum tree (mxv_ppo.hip): `blocks` workgroups, no striding
+    template <typename Args>
+    int launch_blocks(const void *kernel, Args &a, int64_t blocks, void *stream) const {
+        void *args[] = {&a};
+        const hipError_t e = hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3(rule::kThreads), args, 0, (hipStream_t)stream);
         return e == hipSuccess ? MXV_OK : hip_failed("kernel launch", e);
     }
 
