@@ -40,12 +40,17 @@ _LAZY = {
     "ppo_clip_loss": ("gym_amd.ppo", "ppo_clip_loss"),
 }
 
-
 def __getattr__(name):
     if name in ("vector", "wrappers", "spaces", "error", "plugin", "toy_text"):  # sub-modules, gym-shaped
         import importlib
 
         return importlib.import_module(f"gym_amd.{name}")
+    if name == "vtrace":
+        # the function shares its sub-module's name, and importing a sub-module binds it as the package's attribute: the module is
+        # callable (gym_amd/vtrace.py), so gym_amd.vtrace(...) is the function before and after that import
+        import importlib
+
+        return importlib.import_module("gym_amd.vtrace")
     if name in _LAZY:
         import importlib
 

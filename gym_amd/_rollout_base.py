@@ -68,6 +68,18 @@ class _RolloutBase:
         return gae(traj["reward"], traj["terminated"], traj["truncated"], values, last_value, gamma=gamma, lam=lam,
                    final_values=final_values, out=out)
 
+    def vtrace(self, traj, values, log_prob, old_log_prob, last_value=None, *, gamma: float = 0.99, lam: float = 1.0, rho_bar: float = 1.0,
+               c_bar: float = 1.0, pg_rho_bar=None, final_values=None, out=None):
+        """V-trace targets of the chunk in `traj` -> (vs, pg_advantages), float32 [K, N]: gym_amd.vtrace.vtrace on traj["reward"],
+        traj["terminated"], traj["truncated"] after ready().  For a chunk whose actions were drawn by older weights than the ones being
+        updated: `old_log_prob` [K, N] is what the sampler recorded, `log_prob` [K, N] the learner's log pi of the stored actions
+        (evaluate_categorical / evaluate_gaussian); `values`, `last_value` and `final_values` as in advantages()."""
+        from .vtrace import vtrace
+
+        self.ready()
+        return vtrace(log_prob, old_log_prob, traj["reward"], traj["terminated"], traj["truncated"], values, last_value, gamma=gamma,
+                      lam=lam, rho_bar=rho_bar, c_bar=c_bar, pg_rho_bar=pg_rho_bar, final_values=final_values, out=out)
+
     def returns_to_go(self, traj, *, gamma: float = 0.99, last_value=None, final_values=None, out=None):
         """Discounted returns-to-go of the chunk in `traj` -> float32 [K, N]: gym_amd.returns.discounted_returns after ready()."""
         from .returns import discounted_returns
