@@ -38,6 +38,7 @@ _LAZY = {
     "evaluate_gaussian": ("gym_amd.policy_eval", "evaluate_gaussian"),
     "advantage_moments": ("gym_amd.ppo", "advantage_moments"),
     "ppo_clip_loss": ("gym_amd.ppo", "ppo_clip_loss"),
+    "dqn_loss": ("gym_amd.dqn", "dqn_loss"),
 }
 
 def __getattr__(name):

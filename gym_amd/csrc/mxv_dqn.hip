@@ -1,0 +1,469 @@
+// mxv_dqn.hip — the Q-learning loss of a batch: TD targets (given, or the one-step bootstrap of DQN / double DQN), the Huber loss of the
+// TD errors, its diagnostics and its dense gradient with respect to q (include/mxv_dqn.h).
+//
+// The results are defined bit for bit by the rule in the header: float64, one rounding per operation (this file is built with
+// -ffp-contract=off like the rest of the library), and every sum the fixed tree of mxv_ppo.hip over the row index — nothing here depends
+// on the order in which lanes or workgroups arrive.  The argument checks are those of mxv_policy_host.hpp.
+//
+// Shape of the kernels (about 12 fp64 operations for 25 + 4 A bytes a row forwards, 8 for 21 + 8 A backwards: bound by memory):
+//   * dqn_leaf<AT>: one workgroup of 256 lanes per leaf of 1024 consecutive rows; lane t takes rows t, t + 256, t + 512, t + 768.  One
+//     lane owns a row: q[i, a_i] is one dword (read at column 0 when the action is out of range, and then replaced), a row of the
+//     selector is one access of A dwords for A = 2, 3, 4, 6 (the straight-line instantiations, as in mxv_policy_eval.hip) and a loop
+//     that keeps nothing per column for every other A (AT = 0).  Then the xor butterfly of each wave (DPP / permlane: no LDS round
+//     trips) and the four waves through LDS: 4 x 8 doubles.  A leaf writes its 8 partials to the workspace and, if asked, td_error.
+//   * dqn_tree: one workgroup per group of 1024 partials; the last level (one group) also finishes the loss and the diagnostics in its
+//     first lane.  So a forward is 2 launches up to 2^20 rows, 3 up to 2^30.
+//   * dqn_bwd<AT>: recomputes the row and writes the dense [M, A] gradient.  A = 2, 3, 4, 6: a lane holds its row of the gradient in
+//     registers and stores it as one access of A dwords — consecutive lanes, consecutive rows: a wave's stores are 64 A consecutive
+//     dwords.  Every other A: a lane leaves its row's one value and its column in LDS (256 x 8 bytes), and the workgroup then writes the
+//     tile's 256 A consecutive floats with lane t taking elements t, t + 256, ...: every wave store is a dense burst of 64 dwords,
+//     whatever A is.
+//   * everything in the rule is a select; which optional inputs there are is a uniform branch.
+//   * wave_tree / four_waves are a copy of mxv_ppo.hip's (that file's text is pinned by its resource test); DESIGN.md §17 names the
+//     shared header as deferred work.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/mxv_dqn.h"
+#include "mxv_policy_host.hpp"
+#include "mxv_policy_rule.hpp"
+
+namespace {
+
+using namespace mxv::rule;
+using namespace mxv::policy_host;
+
+constexpr int kLeafRows = 1024;      // rows per leaf: four per lane
+constexpr int kTreeFan = 1024;       // partials folded per workgroup per tree level: four per lane
+constexpr int kV = MXV_DQN_STATS;    // partials of a leaf: sums of term, ae, qa, y, lin; max ae, min qa, max qa
+
+struct DqnArgs {
+    const float *q, *targets, *reward, *next_q, *online, *weights;
+    const void *actions;
+    const uint8_t *terminated;
+    const float *g;                  // backward: the incoming gradient of the loss, one float32
+    double *partials;                // forward: [leaves][8]
+    float *td_error;                 // forward, optional
+    float *grad;                     // backward: [M][A], contiguous
+    double gamma, delta;
+    int64_t M, q_ld, next_ld, online_ld, tiles;
+    int32_t A, i64;
+};
+
+struct TreeArgs {
+    const double *in;                // [count][8]
+    double *out;                     // [groups][8]; unused by the last level
+    int64_t count, M;
+    int32_t last;
+    float *loss, *stats;
+};
+
+__device__ __forceinline__ double nan64() { return __longlong_as_double(0x7FF8000000000000ll); }
+// round to nearest even; every NaN leaves as the one pattern
+__device__ __forceinline__ float to_f32(double x) {
+    const float y = (float)x;
+    return y != y ? __uint_as_float(0x7FC00000u) : y;
+}
+
+struct Add {
+    static __device__ __forceinline__ double identity() { return 0.0; }
+    static __device__ __forceinline__ double op(double a, double b) { return a + b; }
+};
+struct Min {   // operands are never NaN (a NaN is skipped at its row); two zeros of either sign are one value: the finish writes +0.0
+    static __device__ __forceinline__ double identity() { return (double)__builtin_inff(); }
+    static __device__ __forceinline__ double op(double a, double b) { return b < a ? b : a; }
+};
+struct Max {
+    static __device__ __forceinline__ double identity() { return -(double)__builtin_inff(); }
+    static __device__ __forceinline__ double op(double a, double b) { return b > a ? b : a; }
+};
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+
+// The xor butterfly over lane bits 0..5 = the pairwise tree over the lane index of a wave; every lane ends with the tree's value.
+// Stages 1, 2: quad permutes.  Stages 4, 8: after them every lane of a quad (of a half row) holds the same partial, so the mirror
+// permutes deliver what lane ^ 4 (lane ^ 8) holds.  Stages 16, 32: v_permlane16_swap / v_permlane32_swap.  Op commutes, so the value
+// is that of the lane ^ (1 << b) form of the rule.
+template <class Op>
+__device__ __forceinline__ double wave_tree(double v) {
+    v = Op::op(v, dpp_f64<0xB1>(v));     // quad_perm [1, 0, 3, 2]
+    v = Op::op(v, dpp_f64<0x4E>(v));     // quad_perm [2, 3, 0, 1]
+    v = Op::op(v, dpp_f64<0x141>(v));    // row_half_mirror
+    v = Op::op(v, dpp_f64<0x140>(v));    // row_mirror
+    {
+        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v = Op::op(__hiloint2double((int)b[0], (int)a[0]), __hiloint2double((int)b[1], (int)a[1]));   // rows (0, 1), (2, 3)
+    }
+    {
+        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        v = Op::op(__hiloint2double((int)b[0], (int)a[0]), __hiloint2double((int)b[1], (int)a[1]));   // lower half, upper half
+    }
+    return v;
+}
+
+template <class Op>
+__device__ __forceinline__ double four_waves(const double (*sm)[kV], int v) {
+    return Op::op(Op::op(sm[0][v], sm[1][v]), Op::op(sm[2][v], sm[3][v]));
+}
+
+// the operation of partial v
+__device__ __forceinline__ double combine(const double (*sm)[kV], int v) {
+    return v == MXV_DQN_Q_TAKEN_MIN ? four_waves<Min>(sm, v) : (v == MXV_DQN_TD_ABS_MAX || v == MXV_DQN_Q_TAKEN_MAX) ? four_waves<Max>(sm, v) : four_waves<Add>(sm, v);
+}
+
+// ---- one row of the rule ----
+struct Row {
+    double qa, y, e, ae, h, dh;
+    int32_t col;      // the stored action, or -1 for anything outside 0..A-1
+};
+
+// the first maximum of a selector row and whether the row holds a NaN
+template <int AT>
+__device__ __forceinline__ void first_max(const float *sel, int A, float &best, int &jmax, bool &bad) {
+    if constexpr (AT > 0) {
+        float x[AT];
+#pragma unroll
+        for (int k = 0; k < AT; ++k) x[k] = sel[k];      // merged into one access of AT dwords (two for AT = 6): 4-byte alignment suffices
+        best = x[0];
+        jmax = 0;
+        bad = x[0] != x[0];
+#pragma unroll
+        for (int k = 1; k < AT; ++k) {
+            bad |= x[k] != x[k];
+            const bool up = x[k] > best;
+            best = up ? x[k] : best;
+            jmax = up ? k : jmax;
+        }
+    } else {
+        best = sel[0];
+        jmax = 0;
+        bad = best != best;
+        for (int k = 1; k < A; ++k) {
+            const float x = sel[k];
+            bad |= x != x;
+            const bool up = x > best;
+            best = up ? x : best;
+            jmax = up ? k : jmax;
+        }
+    }
+}
+
+template <int AT>
+__device__ __forceinline__ Row row_of(const DqnArgs &p, int64_t i) {
+    const int A = AT > 0 ? AT : p.A;
+    Row w;
+    const int64_t v = p.i64 ? static_cast<const int64_t *>(p.actions)[i] : (int64_t) static_cast<const int32_t *>(p.actions)[i];
+    const bool ok = v >= 0 && v < (int64_t)A;
+    w.col = ok ? (int32_t)v : -1;
+    const float qf = p.q[i * p.q_ld + (ok ? v : 0)];      // one dword; a bad action reads column 0 and is replaced
+    w.qa = ok ? (double)qf : nan64();
+    if (p.targets) {      // uniform: the target mode
+        w.y = (double)p.targets[i];
+    } else {
+        const bool dbl = p.online != nullptr;      // uniform
+        const float *sel = dbl ? p.online + i * p.online_ld : p.next_q + i * p.next_ld;
+        float best;
+        int jmax;
+        bool bad;
+        first_max<AT>(sel, A, best, jmax, bad);
+        // one dword, also when next_q itself selects (the row was just read: a cache hit).  `dbl ? load : best` makes the compiler select
+        // between the two ADDRESSES and park best in scratch for it.
+        const float nq = p.next_q[i * p.next_ld + jmax];
+        const double nv = bad ? nan64() : (double)nq;
+        const double r = (double)p.reward[i];
+        const double boot = r + p.gamma * nv;
+        w.y = p.terminated[i] ? r : boot;
+    }
+    w.e = w.qa - w.y;
+    w.ae = __builtin_fabs(w.e);
+    const bool nan_e = w.e != w.e, quad = w.ae <= p.delta;
+    const double h = quad ? 0.5 * (w.e * w.e) : p.delta * (w.ae - 0.5 * p.delta);
+    const double dh = quad ? w.e : (w.e < 0.0 ? -p.delta : p.delta);
+    w.h = nan_e ? nan64() : h;
+    w.dh = nan_e ? nan64() : dh;
+    return w;
+}
+
+// ---- forward: the leaves ----
+template <int AT>
+__global__ void __launch_bounds__(kThreads) dqn_leaf(const DqnArgs p) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
+    const bool has_w = p.weights != nullptr;      // uniform
+    double s = 0.0, sa = 0.0, sq = 0.0, sy = 0.0, sl = 0.0, mx_ae = Max::identity(), mn_q = Min::identity(), mx_q = Max::identity();
+#pragma unroll
+    for (int j = 0; j < kLeafRows / kThreads; ++j) {
+        const int64_t i = row0 + j * kThreads + tid;
+        if (i >= p.M) continue;
+        const Row w = row_of<AT>(p, i);
+        const double term = has_w ? (double)p.weights[i] * w.h : w.h;
+        s = s + term;
+        sa = sa + w.ae;
+        sq = sq + w.qa;
+        sy = sy + w.y;
+        sl = sl + (w.ae > p.delta ? 1.0 : 0.0);
+        mx_ae = w.ae > mx_ae ? w.ae : mx_ae;      // a NaN compares false: skipped
+        mn_q = w.qa < mn_q ? w.qa : mn_q;
+        mx_q = w.qa > mx_q ? w.qa : mx_q;
+        if (p.td_error) p.td_error[i] = to_f32(w.e);
+    }
+    __shared__ double sm[kThreads / 64][kV];
+    const double t[kV] = {wave_tree<Add>(s), wave_tree<Add>(sa), wave_tree<Add>(sq), wave_tree<Add>(sy),
+                          wave_tree<Add>(sl), wave_tree<Max>(mx_ae), wave_tree<Min>(mn_q), wave_tree<Max>(mx_q)};
+    if (lane == 0) {
+#pragma unroll
+        for (int v = 0; v < kV; ++v) sm[wave][v] = t[v];
+    }
+    __syncthreads();
+    if (tid < kV) p.partials[(int64_t)blockIdx.x * kV + tid] = combine(sm, tid);
+}
+
+// ---- forward: one level of the tree; the last one finishes ----
+template <class Op>
+__device__ __forceinline__ double group_value(const TreeArgs &t, int64_t l0, int v) {
+    double a[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = l0 + i < t.count ? t.in[(l0 + i) * kV + v] : Op::identity();
+    return wave_tree<Op>(Op::op(Op::op(a[0], a[1]), Op::op(a[2], a[3])));
+}
+
+__global__ void __launch_bounds__(kThreads) dqn_tree(const TreeArgs t) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t l0 = (int64_t)blockIdx.x * kTreeFan + (int64_t)tid * 4;
+    __shared__ double sm[kThreads / 64][kV];
+#pragma unroll
+    for (int v = 0; v < kV; ++v) {
+        const double x = v == MXV_DQN_Q_TAKEN_MIN ? group_value<Min>(t, l0, v)
+                         : (v == MXV_DQN_TD_ABS_MAX || v == MXV_DQN_Q_TAKEN_MAX) ? group_value<Max>(t, l0, v) : group_value<Add>(t, l0, v);
+        if (lane == 0) sm[wave][v] = x;
+    }
+    __syncthreads();
+    if (!t.last) {
+        if (tid < kV) t.out[(int64_t)blockIdx.x * kV + tid] = combine(sm, tid);
+        return;
+    }
+    if (tid != 0) return;
+    const double Mf = (double)t.M;
+    const double loss = four_waves<Add>(sm, MXV_DQN_LOSS_TERM) / Mf;
+    t.loss[0] = to_f32(loss);
+    t.stats[MXV_DQN_LOSS_TERM] = to_f32(loss);
+    t.stats[MXV_DQN_TD_ABS_MEAN] = to_f32(four_waves<Add>(sm, MXV_DQN_TD_ABS_MEAN) / Mf);
+    t.stats[MXV_DQN_Q_TAKEN_MEAN] = to_f32(four_waves<Add>(sm, MXV_DQN_Q_TAKEN_MEAN) / Mf);
+    t.stats[MXV_DQN_TARGET_MEAN] = to_f32(four_waves<Add>(sm, MXV_DQN_TARGET_MEAN) / Mf);
+    t.stats[MXV_DQN_LINEAR_FRACTION] = to_f32(four_waves<Add>(sm, MXV_DQN_LINEAR_FRACTION) / Mf);
+    t.stats[MXV_DQN_TD_ABS_MAX] = to_f32(four_waves<Max>(sm, MXV_DQN_TD_ABS_MAX) + 0.0);      // + 0.0: a zero of either sign leaves as +0.0
+    t.stats[MXV_DQN_Q_TAKEN_MIN] = to_f32(four_waves<Min>(sm, MXV_DQN_Q_TAKEN_MIN) + 0.0);
+    t.stats[MXV_DQN_Q_TAKEN_MAX] = to_f32(four_waves<Max>(sm, MXV_DQN_Q_TAKEN_MAX) + 0.0);
+}
+
+// ---- backward ----
+// the one value of row i's gradient that is not a zero (its column: w.col; every column is NaN where w.col < 0)
+__device__ __forceinline__ float taken_grad(const DqnArgs &p, const Row &w, int64_t i, double gs, bool has_w) {
+    return to_f32(gs * (has_w ? (double)p.weights[i] * w.dh : w.dh));
+}
+
+template <int AT>
+__global__ void __launch_bounds__(kThreads) dqn_bwd(const DqnArgs p) {
+    const float nan = __uint_as_float(0x7FC00000u);
+    const bool has_w = p.weights != nullptr;      // uniform
+    const double gs = (double)p.g[0] / (double)p.M;
+    if constexpr (AT > 0) {
+        for (int64_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+            const int64_t i = tile * kThreads + threadIdx.x;
+            if (i >= p.M) continue;
+            const Row w = row_of<AT>(p, i);
+            const float val = taken_grad(p, w, i, gs, has_w);
+            float g[AT];
+#pragma unroll
+            for (int k = 0; k < AT; ++k) g[k] = w.col < 0 ? nan : (w.col == k ? val : 0.0f);
+            float *out = p.grad + i * AT;
+#pragma unroll
+            for (int k = 0; k < AT; ++k) out[k] = g[k];      // one store of AT dwords (two for AT = 6)
+        }
+    } else {
+        __shared__ float s_val[kThreads];
+        __shared__ int32_t s_col[kThreads];
+        const int tid = threadIdx.x, A = p.A;
+        const float inv_A = 1.0f / (float)A;
+        for (int64_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {      // the trip count is the workgroup's: the barriers are uniform
+            const int64_t r0 = tile * kThreads, i = r0 + tid;
+            if (i < p.M) {
+                const Row w = row_of<0>(p, i);
+                s_val[tid] = taken_grad(p, w, i, gs, has_w);
+                s_col[tid] = w.col;
+            }
+            __syncthreads();
+            const int64_t left = p.M - r0;
+            const int n = (int)(left < kThreads ? left : kThreads) * A;      // the tile's elements: at most 256 x 64
+            float *out = p.grad + r0 * A;
+            for (int k = tid; k < n; k += kThreads) {
+                // k / A: (k + 0.5) / A is at least 1 / 128 away from an integer and the two float roundings move it by less than 2^-9
+                const int r = (int)(((float)k + 0.5f) * inv_A);
+                const int c = k - r * A, col = s_col[r];
+                out[k] = col < 0 ? nan : (c == col ? s_val[r] : 0.0f);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- host ----
+int64_t leaves_of(int64_t M) { return (M + kLeafRows - 1) / kLeafRows; }
+
+// doubles of workspace per value of a leaf: the leaves, and every level of the tree that is not the last
+int64_t workspace_slots(int64_t M) {
+    int64_t count = leaves_of(M), slots = count;
+    while (count > kTreeFan) {
+        count = (count + kTreeFan - 1) / kTreeFan;
+        slots += count;
+    }
+    return slots;
+}
+
+using DCall = Call<mxv::DqnCall>;
+
+template <int AT> struct Leaf { static const void *ptr() { return reinterpret_cast<const void *>(&dqn_leaf<AT>); } };
+template <int AT> struct Bwd { static const void *ptr() { return reinterpret_cast<const void *>(&dqn_bwd<AT>); } };
+template <template <int> class K>
+const void *pick(int32_t A) {
+    switch (A) {
+        case 2: return K<2>::ptr();
+        case 3: return K<3>::ptr();
+        case 4: return K<4>::ptr();
+        case 6: return K<6>::ptr();
+        default: return K<0>::ptr();
+    }
+}
+
+int check_rows_ld(const DCall &call, const char *name, int64_t ld, int64_t M, int32_t A) {
+    if (ld < A) return call.bad("%s: row stride %s = %lld must be at least A = %d", call.api, name, (long long)ld, (int)A);
+    return call.check_stride(ld, M);
+}
+
+// what the forward and the backward check alike; fills the inputs of `p`
+int check_loss(const DCall &call, int64_t M, int32_t A, const float *q, int64_t q_ld, const void *actions, int32_t action_bytes,
+               const float *targets, const float *reward, const uint8_t *terminated, const float *next_q, int64_t next_q_ld, const float *online,
+               int64_t online_ld, double gamma, double delta, const float *weights, DqnArgs &p) {
+    if (!q) return call.bad("%s: q pointer is NULL", call.api);
+    if (!actions) return call.bad("%s: actions pointer is NULL", call.api);
+    if (M < 1) return call.bad("%s: M = %lld must be at least 1", call.api, (long long)M);
+    if (M > kMaxElems) return call.bad("%s: M = %lld is beyond 2^40 rows", call.api, (long long)M);
+    if (A < 1 || A > kMaxActions) return call.bad("%s: A = %d must be in 1..%d", call.api, (int)A, kMaxActions);
+    if (int rc = check_rows_ld(call, "q_ld", q_ld, M, A)) return rc;
+    if (action_bytes != 4 && action_bytes != 8) return call.bad("%s: action_bytes = %d must be 4 (int32) or 8 (int64)", call.api, (int)action_bytes);
+    const bool any_boot = reward || terminated || next_q;
+    if (targets && any_boot)
+        return call.bad("%s: targets is given together with reward, terminated or next_q: exactly one target mode", call.api);
+    if (targets && online) return call.bad("%s: next_q_online is given with targets: it belongs to the bootstrap mode", call.api);
+    if (!targets && !any_boot) return call.bad("%s: neither targets nor reward, terminated and next_q are given: exactly one target mode", call.api);
+    if (!targets) {
+        if (!reward) return call.bad("%s: reward pointer is NULL in the bootstrap mode", call.api);
+        if (!terminated) return call.bad("%s: terminated pointer is NULL in the bootstrap mode", call.api);
+        if (!next_q) return call.bad("%s: next_q pointer is NULL in the bootstrap mode", call.api);
+        if (int rc = check_rows_ld(call, "next_q_ld", next_q_ld, M, A)) return rc;
+        if (online)
+            if (int rc = check_rows_ld(call, "next_q_online_ld", online_ld, M, A)) return rc;
+    }
+    if (!std::isfinite(gamma)) return call.bad("%s: gamma = %g must be finite", call.api, gamma);
+    if (!(delta > 0.0)) return call.bad("%s: delta = %g must be above 0 (+Inf: the half squared error)", call.api, delta);
+    p.q = q; p.actions = actions; p.targets = targets; p.reward = reward; p.terminated = terminated; p.next_q = next_q; p.online = online;
+    p.weights = weights; p.gamma = gamma; p.delta = delta;
+    p.M = M; p.q_ld = q_ld; p.next_ld = next_q_ld; p.online_ld = online_ld; p.tiles = (M + kThreads - 1) / kThreads;
+    p.A = A; p.i64 = action_bytes == 8;
+    return MXV_OK;
+}
+
+constexpr int kInputs = 9;
+// the byte ranges of the inputs, in the order of the arguments; an absent one has lo == 0
+void input_ranges(const DqnArgs &p, const float *g, Range *r) {
+    const uint64_t mb = (uint64_t)p.M * 4, ab = p.i64 ? 8 : 4;
+    r[0] = {"q", (uintptr_t)p.q, rows_bytes(p.M, p.q_ld, p.A), 4};
+    r[1] = {"actions", (uintptr_t)p.actions, (uint64_t)p.M * ab, ab};
+    r[2] = {"targets", (uintptr_t)p.targets, mb, 4};
+    r[3] = {"reward", (uintptr_t)p.reward, mb, 4};
+    r[4] = {"terminated", (uintptr_t)p.terminated, (uint64_t)p.M, 1};
+    r[5] = {"next_q", (uintptr_t)p.next_q, p.next_q ? rows_bytes(p.M, p.next_ld, p.A) : 0, 4};
+    r[6] = {"next_q_online", (uintptr_t)p.online, p.online ? rows_bytes(p.M, p.online_ld, p.A) : 0, 4};
+    r[7] = {"weights", (uintptr_t)p.weights, mb, 4};
+    r[8] = {"grad_loss", (uintptr_t)g, 4, 4};
+}
+
+int run_tree(const DCall &call, TreeArgs t, double *ws, int64_t leaves, void *stream) {
+    int64_t count = leaves, offset = leaves * kV;
+    const double *in = ws;
+    for (;;) {
+        const int64_t groups = (count + kTreeFan - 1) / kTreeFan;
+        t.in = in; t.count = count; t.last = groups == 1; t.out = t.last ? nullptr : ws + offset;
+        if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&dqn_tree), t, groups, stream)) return rc;
+        if (t.last) return MXV_OK;
+        in = t.out; offset += groups * kV; count = groups;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mxv_dqn_workspace_bytes(int64_t M) { return M < 1 || M > kMaxElems ? 0 : workspace_slots(M) * kV * (int64_t)sizeof(double); }
+
+int mxv_dqn_loss(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t q_ld, const void *actions_dev, int32_t action_bytes,
+                 const float *targets_dev, const float *reward_dev, const uint8_t *terminated_dev, const float *next_q_dev, int64_t next_q_ld,
+                 const float *next_q_online_dev, int64_t next_q_online_ld, double gamma, double delta, const float *weights_dev,
+                 void *workspace_dev, int64_t workspace_bytes, float *td_error_dev, float *loss_out_dev, float *stats_out_dev) {
+    const DCall call{"mxv_dqn_loss", 'M'};
+    DqnArgs p{};
+    if (int rc = check_loss(call, M, A, q_dev, q_ld, actions_dev, action_bytes, targets_dev, reward_dev, terminated_dev, next_q_dev, next_q_ld,
+                            next_q_online_dev, next_q_online_ld, gamma, delta, weights_dev, p))
+        return rc;
+    if (!loss_out_dev) return call.bad("%s: loss_out pointer is NULL", call.api);
+    if (!stats_out_dev) return call.bad("%s: stats_out pointer is NULL", call.api);
+    if (!workspace_dev) return call.bad("%s: workspace pointer is NULL", call.api);
+    const int64_t need = mxv_dqn_workspace_bytes(M);
+    if (workspace_bytes < need)
+        return call.bad("%s: workspace_bytes = %lld is below mxv_dqn_workspace_bytes(%lld) = %lld", call.api, (long long)workspace_bytes, (long long)M, (long long)need);
+    Range ins[kInputs];
+    input_ranges(p, nullptr, ins);
+    const Range outs[] = {{"workspace", (uintptr_t)workspace_dev, (uint64_t)need, 8}, {"td_error", (uintptr_t)td_error_dev, (uint64_t)M * 4, 4},
+                          {"loss_out", (uintptr_t)loss_out_dev, 4, 4}, {"stats_out", (uintptr_t)stats_out_dev, MXV_DQN_STATS * 4, 4}};
+    if (int rc = call.check_ranges(M, ins, kInputs, outs, 4)) return rc;
+    const int64_t leaves = leaves_of(M);
+    p.partials = static_cast<double *>(workspace_dev);
+    p.td_error = td_error_dev;
+    if (int rc = call.launch_blocks(pick<Leaf>(A), p, leaves, stream)) return rc;
+    TreeArgs t{};
+    t.M = M; t.loss = loss_out_dev; t.stats = stats_out_dev;
+    return run_tree(call, t, p.partials, leaves, stream);
+}
+
+int mxv_dqn_loss_backward(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t q_ld, const void *actions_dev, int32_t action_bytes,
+                          const float *targets_dev, const float *reward_dev, const uint8_t *terminated_dev, const float *next_q_dev,
+                          int64_t next_q_ld, const float *next_q_online_dev, int64_t next_q_online_ld, double gamma, double delta,
+                          const float *weights_dev, const float *grad_loss_dev, float *grad_q_dev) {
+    const DCall call{"mxv_dqn_loss_backward", 'M'};
+    DqnArgs p{};
+    if (int rc = check_loss(call, M, A, q_dev, q_ld, actions_dev, action_bytes, targets_dev, reward_dev, terminated_dev, next_q_dev, next_q_ld,
+                            next_q_online_dev, next_q_online_ld, gamma, delta, weights_dev, p))
+        return rc;
+    if (!grad_loss_dev) return call.bad("%s: grad_loss pointer is NULL", call.api);
+    if (!grad_q_dev) return call.bad("%s: grad_q pointer is NULL", call.api);
+    Range ins[kInputs];
+    input_ranges(p, grad_loss_dev, ins);
+    const Range outs[] = {{"grad_q", (uintptr_t)grad_q_dev, (uint64_t)M * (uint64_t)A * 4, 4}};
+    if (int rc = call.check_ranges(M, ins, kInputs, outs, 1)) return rc;
+    p.g = grad_loss_dev; p.grad = grad_q_dev;
+    return call.launch(pick<Bwd>(A), p, stream);
+}
+
+const char *mxv_dqn_last_error(void) { return mxv::last_error<mxv::DqnCall>(nullptr); }
+
+}  // extern "C"

@@ -28,6 +28,9 @@ struct PpoCall {   // include/mxv_ppo.h: mxv_ppo_last_error
 struct VtraceCall {   // include/mxv_vtrace.h: mxv_vtrace_last_error
     std::string error;
 };
+struct DqnCall {   // include/mxv_dqn.h: mxv_dqn_last_error
+    std::string error;
+};
 
 namespace policy_host {
 
