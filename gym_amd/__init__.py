@@ -39,6 +39,7 @@ _LAZY = {
     "advantage_moments": ("gym_amd.ppo", "advantage_moments"),
     "ppo_clip_loss": ("gym_amd.ppo", "ppo_clip_loss"),
     "dqn_loss": ("gym_amd.dqn", "dqn_loss"),
+    "ReplayBuffer": ("gym_amd.replay", "ReplayBuffer"),
 }
 
 def __getattr__(name):

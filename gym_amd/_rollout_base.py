@@ -113,6 +113,20 @@ class _RolloutBase:
                              "use policy_sampler()")
         return GaussianSampler(1, seed=self.handle._action_seed if seed is None else seed, env_offset=self.env_offset, device=self.device)
 
+    def replay_buffer(self, capacity, seed=None):
+        """A gym_amd.replay.ReplayBuffer for this rollout's transitions: its observation shape and dtype, its action dtype, on its
+        device; `seed` defaults to the rollout's action_seed.  buf.add_chunk(first_obs, traj) stores what rollout_per_step /
+        rollout_tape leave in `traj`."""
+        from .replay import ReplayBuffer
+
+        layout = getattr(self, "_replay_obs", None)
+        if layout is None:
+            raise ValueError(f"{type(self).__name__}: replay_buffer() needs trajectories of [K, N, ...] observation rows; build a "
+                             "gym_amd.ReplayBuffer with the shape and dtype of the rows you record")
+        shape, dtype = layout
+        return ReplayBuffer(capacity, shape, obs_dtype=dtype, action_dtype=self._policy_head[1],
+                            seed=self.handle._action_seed if seed is None else seed, device=self.device)
+
     def synchronize(self):
         """Wait for the engine's stream; raises if a step saw an out-of-range action."""
         try:

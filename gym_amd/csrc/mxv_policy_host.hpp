@@ -31,6 +31,9 @@ struct VtraceCall {   // include/mxv_vtrace.h: mxv_vtrace_last_error
 struct DqnCall {   // include/mxv_dqn.h: mxv_dqn_last_error
     std::string error;
 };
+struct ReplayCall {   // include/mxv_replay.h: mxv_replay_last_error
+    std::string error;
+};
 
 namespace policy_host {
 

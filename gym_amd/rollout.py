@@ -64,6 +64,7 @@ class DeviceRollout(_RolloutBase):
             self.action_dtype = torch.float32
         self.env_offset = int(env_offset)
         self._policy_head = (self.NA, self.action_dtype)      # policy_sampler(): Discrete action count (0: Box) and dtype
+        self._replay_obs = ((self.O,), torch.float32)         # replay_buffer(): one observation row of a trajectory
         with torch.cuda.stream(self.stream):
             n = self.num_envs
             self.obs = torch.empty((n, self.O), dtype=torch.float32, device=self.device)

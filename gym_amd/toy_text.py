@@ -419,6 +419,7 @@ class TabularRollout(_RolloutBase):
                                  general_kernel=general_kernel))
         self.env_offset = int(env_offset)
         self._policy_head = (self.mdp.num_actions, self.int_dtype)      # policy_sampler(): what rollout_tape() takes
+        self._replay_obs = ((), self.int_dtype)                         # replay_buffer(): one state index of a trajectory
         with torch.cuda.stream(self.stream):
             self.obs = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
         self.stream.synchronize()

@@ -39,8 +39,10 @@
  *             env and policy step t: u = (word+0.5)*2^-32 picks the action from the cumulative softmax sums (the rule is in that header)
  *   Gaussian policy draws (mxv_policy.h, optional): key = the sampler's seed, ctr = (G_lo, G_hi, t_lo, (t_hi & 0x0fffffff) | 8<<28) with
  *             G = global_env itself: one call per env and policy step t, its four words make up to four normals (Box-Muller; that header)
+ *   replay index draws (mxv_replay.h, optional): key = the buffer's seed, ctr = (g_lo, g_hi, t_lo, (t_hi & 0x0fffffff) | 9<<28) with
+ *             g = j >> 2 and word j & 3 for row j of sample step t: slot = (word * rows stored) >> 32 (the rule is in that header)
  *   stream tags in ctr[3] >> 28: 1 actions, 2 resets, 3 tabular transitions, 4 step noise, 5 Blackjack draws, 6 action bits, 7 policy draws,
- *             8 Gaussian policy draws
+ *             8 Gaussian policy draws, 9 replay index draws
  * t = index of the vector step since the last mxv_seed().  Streams use GLOBAL env indices: any sharding of one logical vector env
  * over several handles / GPUs draws the same numbers.
  *
