@@ -40,6 +40,7 @@ _LAZY = {
     "ppo_clip_loss": ("gym_amd.ppo", "ppo_clip_loss"),
     "dqn_loss": ("gym_amd.dqn", "dqn_loss"),
     "ReplayBuffer": ("gym_amd.replay", "ReplayBuffer"),
+    "PrioritizedReplayBuffer": ("gym_amd.prioritized", "PrioritizedReplayBuffer"),
 }
 
 def __getattr__(name):

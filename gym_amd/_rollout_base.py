@@ -127,6 +127,19 @@ class _RolloutBase:
         return ReplayBuffer(capacity, shape, obs_dtype=dtype, action_dtype=self._policy_head[1],
                             seed=self.handle._action_seed if seed is None else seed, device=self.device)
 
+    def prioritized_replay_buffer(self, capacity, alpha=0.6, eps=1e-6, seed=None):
+        """A gym_amd.prioritized.PrioritizedReplayBuffer for this rollout's transitions: replay_buffer() with proportional draws, importance
+        weights and update_priorities."""
+        from .prioritized import PrioritizedReplayBuffer
+
+        layout = getattr(self, "_replay_obs", None)
+        if layout is None:
+            raise ValueError(f"{type(self).__name__}: prioritized_replay_buffer() needs trajectories of [K, N, ...] observation rows; build a "
+                             "gym_amd.PrioritizedReplayBuffer with the shape and dtype of the rows you record")
+        shape, dtype = layout
+        return PrioritizedReplayBuffer(capacity, shape, obs_dtype=dtype, action_dtype=self._policy_head[1],
+                                       seed=self.handle._action_seed if seed is None else seed, device=self.device, alpha=alpha, eps=eps)
+
     def synchronize(self):
         """Wait for the engine's stream; raises if a step saw an out-of-range action."""
         try:

@@ -34,6 +34,9 @@ struct DqnCall {   // include/mxv_dqn.h: mxv_dqn_last_error
 struct ReplayCall {   // include/mxv_replay.h: mxv_replay_last_error
     std::string error;
 };
+struct PrioCall {   // include/mxv_prio.h: mxv_prio_last_error
+    std::string error;
+};
 
 namespace policy_host {
 

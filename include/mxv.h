@@ -41,8 +41,11 @@
  *             G = global_env itself: one call per env and policy step t, its four words make up to four normals (Box-Muller; that header)
  *   replay index draws (mxv_replay.h, optional): key = the buffer's seed, ctr = (g_lo, g_hi, t_lo, (t_hi & 0x0fffffff) | 9<<28) with
  *             g = j >> 2 and word j & 3 for row j of sample step t: slot = (word * rows stored) >> 32 (the rule is in that header)
+ *   prioritised replay draws (mxv_prio.h, optional): key = the buffer's seed, ctr = (g_lo, g_hi, t_lo, (t_hi & 0x0fffffff) | 10<<28) with
+ *             g = j >> 1 and the 64-bit word made of words 2(j & 1) + 1 and 2(j & 1) for row j of sample step t: the multiply-high of that
+ *             word and the tree's total descends the integer sum tree (the rule is in that header)
  *   stream tags in ctr[3] >> 28: 1 actions, 2 resets, 3 tabular transitions, 4 step noise, 5 Blackjack draws, 6 action bits, 7 policy draws,
- *             8 Gaussian policy draws, 9 replay index draws
+ *             8 Gaussian policy draws, 9 replay index draws, 10 prioritised replay draws
  * t = index of the vector step since the last mxv_seed().  Streams use GLOBAL env indices: any sharding of one logical vector env
  * over several handles / GPUs draws the same numbers.
  *
