@@ -1,11 +1,12 @@
 """gym_amd.sample_gaussian / GaussianSampler on the device against tests/gaussian_host.py, bit for bit — the action bits, the bits of
-log_prob and the bits of entropy: every D, shape class, offset and step, strided views with guarded outputs, degenerate and extreme
-rows, agreement with torch.distributions.Normal, the device step counter under graph replay, checkpoints, and the samplers of the two
-Box envs end to end."""
+log_prob and the bits of entropy: every D, shape class, offset and step, 2048 * 256 + 257 rows (the tile loop strides), strided views
+with guarded outputs, degenerate and extreme rows, agreement with torch.distributions.Normal, the device step counter under graph
+replay, checkpoints, and the samplers of the two Box envs end to end."""
 import numpy as np
 import pytest
 
 import gaussian_host as gh
+import replay_host as rh
 from gaussian_host import bits
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +123,41 @@ def test_views_of_wider_buffers_and_guarded_outputs(torch, D):
                 p = _guard_bits(torch, parent)
                 assert np.all(p[:lead] == GUARD_F32) and np.all(p[lead + N:] == GUARD_F32), (D, off, omit, name)
         assert torch.equal(wm.cpu(), torch.from_numpy(wide_m)) and torch.equal(ws.cpu(), torch.from_numpy(wide_s))      # inputs are read only
+
+
+# kMaxBlocks * kThreads + 257 rows: the tile loop of gaussian_kernel strides (every smaller N above gives each workgroup one tile);
+# workgroup 0 takes a second, full tile (rows 524 288 ..) and workgroup 1 a second tile of one row
+STRIDING = 2048 * 256 + 257
+
+
+def _twin_at_scale(mean, log_std, seed, step, env_offset):
+    """gh.sample_gaussian with the rule's words from replay_host's vectorised Philox4x32-10 (held to Random123's known answers by
+    tests/test_replay_host.py): gh.words makes one Python call per env, 7 s at this N.  Rows of both trips are checked against it."""
+    N = len(mean)
+    G = np.uint64(env_offset) + np.arange(N, dtype=np.uint64)
+    w4 = np.stack(rh.philox4x32_10(G & np.uint64(0xFFFFFFFF), G >> np.uint64(32), step & 0xFFFFFFFF,
+                                   ((step >> 32) & 0x0FFFFFFF) | (gh.STREAM_GAUSSIAN << 28), seed & 0xFFFFFFFF, seed >> 32), axis=1)
+    spot = [0, 1, 255, 256, 2048 * 256 - 1, 2048 * 256, N - 2, N - 1]
+    assert np.array_equal(w4[spot], gh.words(seed, [env_offset + i for i in spot], step))
+    r = gh.evaluate(mean, log_std, w4)
+    return gh.to_f32(r["act"]).reshape(mean.shape), gh.to_f32(r["log_prob"]), gh.to_f32(r["entropy"])
+
+
+@pytest.mark.parametrize("shared", (False, True))
+@pytest.mark.parametrize("D", (1, 4))                                       # the narrowest and the widest instantiation
+def test_above_2048_tiles_every_workgroup_takes_a_second_tile(torch, D, shared):
+    from gym_amd import policy
+
+    N = STRIDING
+    mean, ls = _head(np.random.default_rng(1400 + D), N, D)
+    ls_ref = ls[0] if shared else ls
+    (a, pa), (lp, plp), (en, pen) = _guarded(torch, (N, D), 3), _guarded(torch, (N,), 1), _guarded(torch, (N,), 2)
+    off, step = ((6, 5), (0, 2 ** 32 + 1))[shared]
+    got = policy.sample_gaussian(dev(torch, mean), dev(torch, ls_ref), seed=SEED, step=step, env_offset=off, out=(a, lp, en))
+    _assert_equal(torch, got, _twin_at_scale(mean, ls_ref, SEED, step, off), (N, D, shared))
+    for parent, lead, n, name in ((pa, 3, N * D, "actions"), (plp, 1, N, "log_prob"), (pen, 2, N, "entropy")):
+        p = _guard_bits(torch, parent)
+        assert np.all(p[:lead] == GUARD_F32) and np.all(p[lead + n:] == GUARD_F32), (D, shared, name)      # behind row N - 1 too
 
 
 def test_overlapping_outputs_raise(torch):

@@ -1,6 +1,7 @@
 """gym_amd.policy on the device against tests/policy_host.py, bit for bit — actions, the bits of log_prob and the bits of entropy:
-every shape class and both instantiation kinds, strided views with guarded outputs, non-finite and extreme rows, the device step
-counter under graph replay, checkpoints, and the samplers of the three rollout front ends end to end."""
+every shape class and both instantiation kinds, 2048 * 256 + 257 rows (the tile loop strides), strided views with guarded outputs,
+non-finite and extreme rows, the device step counter under graph replay, checkpoints, and the samplers of the three rollout front
+ends end to end."""
 import numpy as np
 import pytest
 
@@ -136,6 +137,26 @@ def test_views_of_wider_buffers_and_guarded_outputs(torch, A):
         assert torch.equal(wd.cpu(), torch.from_numpy(wide))       # the logits are read only
     with pytest.raises(ValueError, match="overlaps the logits"):
         policy.sample_categorical(xd, seed=0, step=0, out=(torch.zeros(N, dtype=torch.int64, device="cuda:0"), wd.view(-1)[3:3 + N], None))
+
+
+# kMaxBlocks * kThreads + 257 rows: the tile loop of categorical_kernel strides (every smaller N above gives each workgroup one tile);
+# workgroup 0 takes a second, full tile (rows 524 288 ..) and workgroup 1 a second tile of one row
+STRIDING = 2048 * 256 + 257
+
+
+@pytest.mark.parametrize("A,off,step", ((3, 6, 5), (7, 0, 2 ** 32 + 1)))      # the straight-line kernel and the loop over A
+def test_above_2048_tiles_every_workgroup_takes_a_second_tile(torch, A, off, step):
+    from gym_amd import policy
+
+    N = STRIDING
+    x = _logits(np.random.default_rng(1300 + A), N, A)
+    xd = dev(torch, x)
+    (a, pa), (lp, plp), (en, pen) = _guarded(torch, N, torch.int64, 3), _guarded(torch, N, torch.float32, 1), _guarded(torch, N, torch.float32, 2)
+    got = policy.sample_categorical(xd, seed=11 + A, step=step, env_offset=off, out=(a, lp, en))
+    assert policy.last_launch() == (1, A if A == 3 else 0, 2048)
+    _assert_equal(torch, got, ph.sample_categorical(x, seed=11 + A, step=step, env_offset=off), (N, A, off, step))
+    for parent, lead, name in ((pa, 3, "actions"), (plp, 1, "log_prob"), (pen, 2, "entropy")):
+        _assert_guard_intact(torch, parent, lead, N, (A, name))                # behind row N - 1 too
 
 
 @pytest.mark.parametrize("A", (3, 4, 7))

@@ -1,7 +1,8 @@
 """gym_amd.evaluate_categorical / evaluate_gaussian on the device against tests/policy_eval_host.py, bit for bit — log_prob, entropy and
 the gradients of both: every A and D, shape class, action dtype and absent output or incoming gradient; strided views with guarded
-outputs; degenerate rows, bad actions, masks and non-finite values; the samplers' own bits back (the probability ratio 1); autograd
-through a linear head, leading dims and agreement with torch's float64 autograd; graph capture; the PPO example end to end."""
+outputs; 2048 * 256 + 257 rows (the tile loops of all four kernels stride); degenerate rows, bad actions, masks and non-finite
+values; the samplers' own bits back (the probability ratio 1); autograd through a linear head, leading dims and agreement with torch's
+float64 autograd; graph capture; the PPO example end to end."""
 import numpy as np
 import pytest
 
@@ -240,6 +241,81 @@ def test_gaussian_views_of_wider_buffers_and_guarded_outputs(torch, D):
                 _same(torch, gs, want_s, (D, off, skip, "grad_log_std"))
                 _check_row_guards(torch, pgs, off, M, ld_gs, 1, D, (D, off, skip, "grad_log_std guards"))
         assert torch.equal(wmd.cpu(), torch.from_numpy(wm)) and torch.equal(wad.cpu(), torch.from_numpy(wa))
+
+
+# ---- above 2048 tiles ---------------------------------------------------------------------------------------------------------------------------
+# kMaxBlocks * kThreads + 257 rows: the tile loops of the four kernels stride (every smaller M above gives each workgroup one tile);
+# workgroup 0 takes a second, full tile (rows 524 288 ..) and workgroup 1 a second tile of one row
+STRIDING = 2048 * 256 + 257
+SECOND_TRIP = 2048 * 256 + np.array([0, 1, 63, 64, 255, 256])               # rows of the second tiles: both of them, every wave's edge
+
+
+@pytest.mark.parametrize("A", (3, 7))                                       # a straight-line instantiation and the loop over A
+def test_categorical_above_2048_tiles_every_workgroup_takes_a_second_tile(torch, A):
+    from gym_amd import policy_eval
+
+    M = STRIDING
+    rng = np.random.default_rng(1500 + A)
+    x = _logits(rng, M, A)
+    act = rng.integers(0, A, M)
+    x[SECOND_TRIP[0], 1] = np.nan                                           # the degenerate rows sit where only a second trip reaches
+    x[SECOND_TRIP[1]] = -np.inf
+    x[SECOND_TRIP[5], 0] = np.inf
+    act[SECOND_TRIP[2:5]] = (A, -1, 2 ** 40 + 1)
+    gl, gH = rng.standard_normal(M).astype(np.float32), rng.standard_normal(M).astype(np.float32)
+    xd, ad, gl_d, gH_d = dev(torch, x), dev(torch, act), dev(torch, gl), dev(torch, gH)
+    (lp, plp), (en, pen), (g, pg) = _guarded(torch, (M,), 1), _guarded(torch, (M,), 2), _guarded(torch, (M, A), 3)
+    policy_eval.evaluate_categorical(xd, ad, out=(lp, en))
+    want_lp, want_en = pe.categorical(x, act)
+    _same(torch, lp, want_lp, (A, "log_prob"))
+    _same(torch, en, want_en, (A, "entropy"))
+    assert np.all(host_bits(torch, lp)[SECOND_TRIP] == 0x7FC00000) and np.all(host_bits(torch, en)[SECOND_TRIP] == 0x7FC00000)
+    _check_vector_guards(torch, plp, 1, M, (A, "log_prob guards"))          # behind row M - 1 too
+    _check_vector_guards(torch, pen, 2, M, (A, "entropy guards"))
+    for use in ((True, True), (False, True)):                               # both incoming gradients, then one
+        pg.view(torch.int32).fill_(GUARD_F32)
+        rc = policy_eval.lib.mxv_policy_eval_categorical_backward(_stream(torch), M, A, xd.data_ptr(), A, ad.data_ptr(), 1,
+                                                                  gl_d.data_ptr() if use[0] else None, gH_d.data_ptr() if use[1] else None, g.data_ptr(), A)
+        assert rc == 0, policy_eval.lib.mxv_policy_eval_last_error()
+        _same(torch, g, pe.categorical_backward(x, act, gl if use[0] else None, gH if use[1] else None), (A, "grad", use))
+        assert np.all(host_bits(torch, g).reshape(M, A)[SECOND_TRIP] == 0x7FC00000)
+        _check_vector_guards(torch, pg, 3, M * A, (A, "grad guards", use))
+
+
+@pytest.mark.parametrize("D", (1, 3))
+def test_gaussian_above_2048_tiles_every_workgroup_takes_a_second_tile(torch, D):
+    from gym_amd import policy_eval
+
+    M = STRIDING
+    rng = np.random.default_rng(1600 + D)
+    mean, ls, act = _head(rng, M, D)
+    mean[SECOND_TRIP[:3], 0] = (np.nan, np.inf, -np.inf)                    # the degenerate rows sit where only a second trip reaches
+    ls[SECOND_TRIP[3:], D - 1] = (np.nan, 80.0001, -np.inf)
+    gl, gH = rng.standard_normal(M).astype(np.float32), rng.standard_normal(M).astype(np.float32)
+    md, lsd, ad, gl_d, gH_d = dev(torch, mean), dev(torch, ls), dev(torch, act), dev(torch, gl), dev(torch, gH)
+    (lp, plp), (en, pen), (gm, pgm), (gs, pgs) = _guarded(torch, (M,), 1), _guarded(torch, (M,), 2), _guarded(torch, (M, D), 3), _guarded(torch, (M, D), 1)
+    policy_eval.evaluate_gaussian(md, lsd, ad, out=(lp, en))
+    want_lp, want_en = pe.gaussian(mean, ls, act)
+    _same(torch, lp, want_lp, (D, "log_prob"))
+    _same(torch, en, want_en, (D, "entropy"))
+    assert np.all(host_bits(torch, lp)[SECOND_TRIP] == 0x7FC00000) and np.all(host_bits(torch, en)[SECOND_TRIP] == 0x7FC00000)
+    _check_vector_guards(torch, plp, 1, M, (D, "log_prob guards"))          # behind row M - 1 too
+    _check_vector_guards(torch, pen, 2, M, (D, "entropy guards"))
+    for use in ((True, True), (True, False)):                               # both incoming gradients, then one
+        pgm.view(torch.int32).fill_(GUARD_F32)
+        pgs.view(torch.int32).fill_(GUARD_F32)
+        rc = policy_eval.lib.mxv_policy_eval_gaussian_backward(_stream(torch), M, D, md.data_ptr(), D, lsd.data_ptr(), D, ad.data_ptr(), D,
+                                                               gl_d.data_ptr() if use[0] else None, gH_d.data_ptr() if use[1] else None,
+                                                               gm.data_ptr(), D, gs.data_ptr(), D)
+        assert rc == 0, policy_eval.lib.mxv_policy_eval_last_error()
+        want_m, want_s = pe.gaussian_backward(mean, ls, act, gl if use[0] else None, gH if use[1] else None)
+        for got, want, parent, lead, name in ((gm, want_m, pgm, 3, "grad_mean"), (gs, want_s, pgs, 1, "grad_log_std")):
+            _same(torch, got, want, (D, name, use))
+            assert np.all(host_bits(torch, got).reshape(M, D)[SECOND_TRIP] == 0x7FC00000)
+            _check_vector_guards(torch, parent, lead, M * D, (D, name, "guards", use))
+    # the shared log_std row: a second launch shape of the same loops (log_std_ld = 0)
+    lp2, _ = policy_eval.evaluate_gaussian(md, lsd[7], ad)
+    _same(torch, lp2, pe.gaussian(mean, ls[7], act)[0], (D, "shared log_std"))
 
 
 # ---- edge rows --------------------------------------------------------------------------------------------------------------------------------
