@@ -41,6 +41,8 @@ _LAZY = {
     "dqn_loss": ("gym_amd.dqn", "dqn_loss"),
     "ReplayBuffer": ("gym_amd.replay", "ReplayBuffer"),
     "PrioritizedReplayBuffer": ("gym_amd.prioritized", "PrioritizedReplayBuffer"),
+    "categorical_dqn_loss": ("gym_amd.c51", "categorical_dqn_loss"),
+    "categorical_q_values": ("gym_amd.c51", "categorical_q_values"),
 }
 
 def __getattr__(name):

@@ -1,0 +1,316 @@
+"""The categorical (C51) Q-learning loss of a batch, its diagnostics and its gradient, fused (include/mxv_c51.h): the target
+distribution (given, or the one-step bootstrap of DQN / double DQN projected onto the support), the cross-entropy of the taken action's
+distribution against it, and the dense gradient with respect to the logits — the distributional counterpart of gym_amd.dqn_loss.
+
+    batch       = buffer.sample(256)                                                           # gym_amd.PrioritizedReplayBuffer
+    loss, stats = gym_amd.categorical_dqn_loss(logits, actions, v_min=0.0, v_max=100.0, reward=r, terminated=term, next_logits=target_net,
+                                               next_logits_online=online_net, weights=batch.weights, row_loss=row_loss)
+    loss.backward()                                                                            # one launch: d loss / d logits, dense [M, A, Z]
+    buffer.update_priorities(batch.indices, row_loss)
+    q           = gym_amd.categorical_q_values(logits, v_min=0.0, v_max=100.0)                # [..., A]: what the agent acts greedily on
+
+The arithmetic is float64 in a fixed order, every sum a fixed tree: bit-equal to tests/c51_host.py, a function of the inputs and their
+positions.  `stats` is one device vector of the diagnostics (LOSS_TERM .. Q_TAKEN_MAX index it), read when the caller chooses.  The
+loss is a torch.autograd.Function that saves only its inputs — the backward recomputes the rows and reads the incoming gradient from
+device memory.  Everything launches on the caller's current stream without a synchronisation.  The header is optional (mxv.h does not
+include it), so its symbols are bound here, over the same library as gym_amd._native, and are not part of _native.EXPORTS.  Importing
+this module does not import torch.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _native
+from ._policy_args import MAX_ACTIONS, _one_device, _ptr, _vector
+from ._policy_args import _check as _raise
+from .dqn import _no_grad_input
+from .returns import _scalar
+
+C51_EXPORTS = ("mxv_c51_workspace_bytes", "mxv_c51_loss", "mxv_c51_loss_backward", "mxv_c51_q_values", "mxv_c51_last_error")
+# indices into stats (MXV_C51_* of the header)
+LOSS_TERM, Q_TAKEN_MEAN, TARGET_MEAN, ENTROPY_MEAN, CLIPPED_MASS_MEAN, ROW_LOSS_MAX, Q_TAKEN_MIN, Q_TAKEN_MAX = range(8)
+STATS = 8
+STAT_NAMES = ("loss_term", "q_taken_mean", "target_mean", "entropy_mean", "clipped_mass_mean", "row_loss_max", "q_taken_min", "q_taken_max")
+MIN_ATOMS, MAX_ATOMS = 2, 64
+# the launch shape (gym_amd/csrc/mxv_c51.hip, mxv_policy_rule.hpp)
+LEAF_ROWS = 1024        # rows per leaf of the sum tree, and leaves per group of a level (kLeafRows, kTreeFan)
+TILE_ROWS = 4           # rows (loss, backward) or (row, action) pairs (categorical_q_values) per workgroup: one per wave (kWaves)
+GRID_X = 1 << 16        # tiles along x of the grid of the rows and the backward kernels: beyond, the grid grows along y (kGridX)
+MAX_BLOCKS = 2048       # workgroups of categorical_q_values, which stride over its tiles (kMaxBlocks)
+
+lib = _native.lib
+_P, _D, _I64, _I32 = C.c_void_p, C.c_double, C.c_int64, C.c_int32
+_INPUTS = [_P, _I64, _I32, _I32, _P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P, _I64, _D, _D, _D, _P]      # stream .. weights
+lib.mxv_c51_workspace_bytes.argtypes = [_I64]
+lib.mxv_c51_workspace_bytes.restype = _I64
+lib.mxv_c51_loss.argtypes = _INPUTS + [_P, _I64, _P, _P, _P, _P]
+lib.mxv_c51_loss.restype = C.c_int
+lib.mxv_c51_loss_backward.argtypes = _INPUTS + [_P, _P]
+lib.mxv_c51_loss_backward.restype = C.c_int
+lib.mxv_c51_q_values.argtypes = [_P, _I64, _I32, _I32, _P, _I64, _D, _D, _P]
+lib.mxv_c51_q_values.restype = C.c_int
+lib.mxv_c51_last_error.argtypes = []
+lib.mxv_c51_last_error.restype = C.c_char_p
+
+
+def _check(rc: int):
+    _raise(rc, lib.mxv_c51_last_error)
+
+
+def workspace_bytes(rows: int) -> int:
+    """Bytes of `workspace=` that a batch of `rows` rows needs (six float64 per row, and the partial sums of the leaves)."""
+    n = int(lib.mxv_c51_workspace_bytes(int(rows)))
+    if n == 0:
+        raise ValueError(f"rows must be in 1..2^40, got {rows!r}")
+    return n
+
+
+def launches(rows: int) -> int:
+    """Kernel launches of one forward on `rows` rows: the rows, the leaves (which finish a batch of one leaf), then one per level of the
+    tree: 2 up to 1024 rows, 3 up to 2^20, 4 up to 2^30.  The backward and categorical_q_values are always one."""
+    workspace_bytes(rows)
+    count, n = -(-int(rows) // LEAF_ROWS), 2
+    if count == 1:
+        return n
+    n += 1
+    while count > LEAF_ROWS:
+        count, n = -(-count // LEAF_ROWS), n + 1
+    return n
+
+
+def _workspace(t, workspace, M, dev):
+    """The caller's workspace (a contiguous 1-D uint8 or float64 tensor that is large enough), or a fresh one."""
+    need = workspace_bytes(M)
+    if workspace is None:
+        return t.empty(need // 8, dtype=t.float64, device=dev), need
+    w = _vector(t, workspace, "workspace", getattr(workspace, "shape", ()), (t.uint8, t.float64))
+    if w.dim() != 1 or tuple(workspace.shape) != tuple(w.shape):
+        raise ValueError(f"workspace must be 1-D, got shape {tuple(workspace.shape)}")
+    have = w.numel() * w.element_size()
+    if have < need:
+        raise ValueError(f"workspace holds {have} bytes, {M} rows need {need} (gym_amd.c51.workspace_bytes)")
+    return w, have
+
+
+def _heads(t, x, name):
+    """A float32 [..., A, Z] tensor as its [M, A, Z] rows: the last two dims contiguous; 3-D tensors may have strided rows (views into
+    wider buffers), more dims must flatten without a copy."""
+    what = f"[..., A, Z] with at least one row, 1 <= A <= {MAX_ACTIONS} and {MIN_ATOMS} <= Z <= {MAX_ATOMS}"
+    if not isinstance(x, t.Tensor):
+        raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
+    if x.dtype != t.float32:
+        raise ValueError(f"{name} must be torch.float32, got {x.dtype}")
+    if x.dim() < 3 or x.numel() == 0 or not 1 <= x.shape[-2] <= MAX_ACTIONS or not MIN_ATOMS <= x.shape[-1] <= MAX_ATOMS:
+        raise ValueError(f"{name} must have shape {what}, got {tuple(x.shape)}")
+    A, Z = x.shape[-2:]
+    if x.dim() == 3:
+        x3 = x
+    else:
+        try:
+            x3 = x.view(-1, A, Z)
+        except RuntimeError:
+            raise ValueError(f"{name} of shape {tuple(x.shape)} with strides {tuple(x.stride())} cannot be viewed as [M, {A}, {Z}] rows "
+                             f"(view(-1, {A}, {Z}) fails): pass a contiguous tensor") from None
+    if x3.stride(2) != 1 or (A > 1 and x3.stride(1) != Z):
+        raise ValueError(f"{name} must be contiguous in its last two dimensions (strides {tuple(x3.stride())}): rows may be strided "
+                         "views, actions and atoms not")
+    if x3.shape[0] > 1 and x3.stride(0) < A * Z:
+        raise ValueError(f"{name} has row stride {x3.stride(0)} < {A * Z}: rows overlap")
+    return x3
+
+
+def _ld3(x3):
+    return x3.stride(0) if x3.shape[0] > 1 else x3.shape[1] * x3.shape[2]
+
+
+def _support(v_min, v_max):
+    lo, hi = _scalar("v_min", v_min), _scalar("v_max", v_max)
+    if not lo < hi:
+        raise ValueError(f"v_min must be below v_max, got v_min = {v_min!r}, v_max = {v_max!r}")
+    return lo, hi
+
+
+class _Inputs:
+    """The checked inputs of one call, as the C entry points take them."""
+
+    TENSORS = ("logits", "act", "target_probs", "reward", "term", "next", "online", "weights")
+    SCALARS = ("M", "A", "Z", "gamma", "v_min", "v_max", "dev")
+
+    def call_args(self, t):
+        s = self
+        return (t.cuda.current_stream(s.dev).cuda_stream, s.M, s.A, s.Z, s.logits.data_ptr(), _ld3(s.logits), s.act.data_ptr(),
+                s.act.element_size(), _ptr(s.target_probs), _ptr(s.reward), _ptr(s.term), _ptr(s.next), 0 if s.next is None else _ld3(s.next),
+                _ptr(s.online), 0 if s.online is None else _ld3(s.online), s.gamma, s.v_min, s.v_max, _ptr(s.weights))
+
+
+def _forward(t, a, ws, ws_bytes, row_loss, projected, loss, stats):
+    with t.cuda.device(a.dev):
+        _check(lib.mxv_c51_loss(*a.call_args(t), ws.data_ptr(), ws_bytes, _ptr(row_loss), _ptr(projected), loss.data_ptr(), stats.data_ptr()))
+
+
+_FUNCTION = None
+
+
+def _function():
+    """The torch.autograd.Function, made at the first differentiable call: importing this module does not import torch."""
+    global _FUNCTION
+    if _FUNCTION is not None:
+        return _FUNCTION
+    import torch as t
+    from torch.autograd.function import once_differentiable
+
+    class CategoricalDqnLoss(t.autograd.Function):
+        @staticmethod
+        def forward(ctx, logits, a, row_loss, projected):
+            ctx.set_materialize_grads(False)
+            loss = t.empty((), dtype=t.float32, device=a.dev)
+            stats = t.empty(STATS, dtype=t.float32, device=a.dev)
+            ws, ws_bytes = _workspace(t, None, a.M, a.dev)
+            _forward(t, a, ws, ws_bytes, row_loss, projected, loss, stats)
+            ctx.save_for_backward(*(getattr(a, k) for k in a.TENSORS))      # the inputs alone: the backward recomputes the rows
+            ctx.scalars = tuple(getattr(a, k) for k in a.SCALARS)
+            ctx.mark_non_differentiable(stats)
+            return loss, stats
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_loss, _g_stats):
+            if g_loss is None or not ctx.needs_input_grad[0]:
+                return None, None, None, None
+            a = _Inputs()
+            for k, v in zip(a.TENSORS + a.SCALARS, ctx.saved_tensors + ctx.scalars):
+                setattr(a, k, v)
+            g = g_loss.contiguous()      # one float32 in device memory: read by the kernel, never by the host
+            grad = t.empty((a.M, a.A, a.Z), dtype=t.float32, device=a.dev)      # contiguous; every element is written
+            with t.cuda.device(a.dev):
+                _check(lib.mxv_c51_loss_backward(*a.call_args(t), g.data_ptr(), grad.data_ptr()))
+            return grad, None, None, None
+
+    _FUNCTION = CategoricalDqnLoss
+    return _FUNCTION
+
+
+def categorical_dqn_loss(logits, actions, *, v_min, v_max, target_probs=None, reward=None, terminated=None, next_logits=None,
+                         next_logits_online=None, gamma=0.99, weights=None, row_loss=None, projected=None, workspace=None, out=None):
+    """The categorical (C51) loss mean(weights * cross_entropy(m[i], softmax(logits[i, actions[i]]))) and its diagnostics -> (loss, stats).
+
+    logits float32 [M, A, Z] (the last two dims contiguous; rows may be strided views into a wider buffer) or [..., A, Z] with any
+    leading dims that view(-1, A, Z) accepts, 1 <= A <= 64 actions, 2 <= Z <= 64 atoms (Z > 64 is out of scope: an atom is a lane of one
+    wave), on the device; actions int64 or int32 of the leading shape, contiguous.  v_min < v_max, finite and required: the support is
+    z_k = v_min + k (v_max - v_min) / (Z - 1).  Exactly one target mode:
+      * target_probs= float32 [..., Z]: the target distribution m on the support, projected by the caller (n-step or otherwise); it is
+        not checked to sum to 1;
+      * reward float32, terminated bool or uint8 (both of the leading shape) and next_logits float32 of logits' shape (strided rows
+        allowed): the target network at the next observation.  The next action is the first maximum of the expected values of
+        next_logits — of next_logits_online (the online network at the next observation) if given: double DQN — and m is the projection
+        of reward + gamma z_j under next_logits' distribution of that action; a terminated row puts all its mass at the reward and
+        ignores both next tensors entirely; a NaN or +Inf anywhere in the selecting row (or a row of only -Inf) makes m NaN.
+    There is no `truncated` argument on purpose: at a truncated step the caller evaluates next_logits on the final observation
+    (final_obs) and leaves terminated unset, as with gym_amd.dqn_loss.
+    weights: float32 of the leading shape or None — importance weights of the rows (PrioritizedReplayBuffer.sample); the mean still
+    divides by M.  row_loss: a float32 tensor of the leading shape to receive the unweighted cross-entropy of each row (>= 0; what goes
+    to update_priorities), or None.  projected: a float32 [..., Z] tensor to receive the m the kernel used, or None.  Only logits may
+    require grad.
+
+    loss is a 0-dim float32 tensor, differentiable with respect to logits: the gradient is dense [M, A, Z] — zero outside the taken
+    action, NaN in the taken action's Z columns of a NaN row, NaN in all A * Z elements of a row whose action is outside 0..A-1.  stats
+    is float32 [8], not differentiable: loss_term (the loss again), q_taken_mean, target_mean, entropy_mean (of the taken action's
+    distribution: it tells a collapsed head), clipped_mass_mean (the target probability whose shifted atom fell outside [v_min, v_max]:
+    it tells a support that is too narrow), row_loss_max, q_taken_min, q_taken_max — LOSS_TERM .. Q_TAKEN_MAX of this module; the
+    extrema skip NaN rows.  out=(loss, stats) and workspace= (a 1-D uint8 or float64 tensor of workspace_bytes(rows) bytes) are accepted
+    only when logits does not require grad; with both the call allocates nothing.  Float64 arithmetic in a fixed order and fixed sum
+    trees, bit-equal to tests/c51_host.py.  2 launches up to 1024 rows, 3 up to 2^20, 4 up to 2^30, and one for the backward, on the
+    current stream; no synchronisation."""
+    import torch as t
+
+    f32 = (t.float32,)
+    a = _Inputs()
+    a.logits = _heads(t, logits, "logits")
+    lead = logits.shape[:-2]
+    a.M, a.A, a.Z = a.logits.shape
+    a.act = _vector(t, actions, "actions", lead, (t.int64, t.int32))
+    boot = {"reward": reward, "terminated": terminated, "next_logits": next_logits}
+    if target_probs is not None:
+        given = [k for k, v in boot.items() if v is not None]
+        if given:
+            raise ValueError(f"target_probs is given together with {', '.join(given)}: exactly one target mode")
+        if next_logits_online is not None:
+            raise ValueError("next_logits_online is given with target_probs: it belongs to the bootstrap mode (reward, terminated, next_logits)")
+    else:
+        missing = [k for k, v in boot.items() if v is None]
+        if len(missing) == 3:
+            raise ValueError("neither target_probs nor reward, terminated and next_logits are given: exactly one target mode")
+        if missing:
+            raise ValueError(f"the bootstrap mode needs reward, terminated and next_logits: {', '.join(missing)} missing")
+    a.target_probs = None if target_probs is None else _vector(t, target_probs, "target_probs", tuple(lead) + (a.Z,), f32)
+    a.reward = None if reward is None else _vector(t, reward, "reward", lead, f32)
+    if isinstance(terminated, t.Tensor) and terminated.dtype == t.bool:
+        terminated = terminated.view(t.uint8)
+    a.term = None if terminated is None else _vector(t, terminated, "terminated", lead, (t.uint8,))
+    a.next = a.online = None
+    for name, x in (("next_logits", next_logits), ("next_logits_online", next_logits_online)):
+        if x is None:
+            continue
+        x3 = _heads(t, x, name)
+        if tuple(x.shape) != tuple(logits.shape):
+            raise ValueError(f"{name} must have shape {tuple(logits.shape)} like logits, got {tuple(x.shape)}")
+        setattr(a, "next" if name == "next_logits" else "online", x3)
+    a.weights = None if weights is None else _vector(t, weights, "weights", lead, f32)
+    a.gamma = _scalar("gamma", gamma)
+    a.v_min, a.v_max = _support(v_min, v_max)
+    rl = None if row_loss is None else _vector(t, row_loss, "row_loss", lead, f32)
+    pj = None if projected is None else _vector(t, projected, "projected", tuple(lead) + (a.Z,), f32)
+    for x, name in ((actions, "actions"), (target_probs, "target_probs"), (reward, "reward"), (next_logits, "next_logits"),
+                    (next_logits_online, "next_logits_online"), (weights, "weights"), (row_loss, "row_loss"), (projected, "projected")):
+        _no_grad_input(t, x, name)
+    grads = t.is_grad_enabled() and logits.requires_grad
+    loss = stats = None
+    if out is not None or workspace is not None:
+        if grads:
+            raise ValueError("out= and workspace= cannot be used when logits requires grad: autograd owns the outputs")
+    if out is not None:
+        out = tuple(out)
+        if len(out) != 2:
+            raise ValueError(f"out must hold 2 entries (loss, stats), got {len(out)}")
+        loss = _vector(t, out[0], "out (loss)", (), f32)
+        stats = _vector(t, out[1], "out (stats)", (STATS,), f32)
+    a.dev = _one_device((("logits", a.logits), ("actions", a.act), ("target_probs", a.target_probs), ("reward", a.reward),
+                         ("terminated", a.term), ("next_logits", a.next), ("next_logits_online", a.online), ("weights", a.weights),
+                         ("row_loss", rl), ("projected", pj), ("out (loss)", loss), ("out (stats)", stats),
+                         ("workspace", workspace if isinstance(workspace, t.Tensor) else None)))
+    if grads:
+        rows, a.logits = a.logits, a.logits.detach()
+        return _function().apply(rows, a, rl, pj)
+    a.logits = a.logits.detach()
+    ws, ws_bytes = _workspace(t, workspace, a.M, a.dev)
+    if out is None:
+        loss = t.empty((), dtype=t.float32, device=a.dev)
+        stats = t.empty(STATS, dtype=t.float32, device=a.dev)
+    _forward(t, a, ws, ws_bytes, rl, pj, loss, stats)
+    return out if out is not None else (loss, stats)
+
+
+def categorical_q_values(logits, *, v_min, v_max, out=None):
+    """The expected action values of a categorical head: float32 [..., A] = sum_k softmax(logits[..., a, :])[k] * z_k, in one launch.
+
+    logits float32 [..., A, Z] as categorical_dqn_loss takes them (1 <= A <= 64, 2 <= Z <= 64), v_min < v_max finite and required.  A row
+    with a NaN or +Inf, or of only -Inf, gives NaN.  The values are the Q_a of the loss's selecting pass, computed by the same lines:
+    the action an agent takes greedily from them (the first maximum) is the j* the loss selects.  out= a float32 tensor of the leading
+    shape + (A,), contiguous; without it one is allocated.  Not differentiable.  On the current stream; no synchronisation."""
+    import torch as t
+
+    x3 = _heads(t, logits, "logits").detach()
+    M, A, Z = x3.shape
+    lo, hi = _support(v_min, v_max)
+    shape = tuple(logits.shape[:-1])
+    if out is None:
+        _one_device((("logits", x3),))
+        out = t.empty(shape, dtype=t.float32, device=x3.device)
+        q = out.view(-1)
+    else:
+        q = _vector(t, out, "out", shape, (t.float32,))
+        _no_grad_input(t, out, "out")
+        _one_device((("logits", x3), ("out", q)))
+    with t.cuda.device(x3.device):
+        _check(lib.mxv_c51_q_values(t.cuda.current_stream(x3.device).cuda_stream, M, A, Z, x3.data_ptr(), _ld3(x3), lo, hi, q.data_ptr()))
+    return out

@@ -37,6 +37,9 @@ struct ReplayCall {   // include/mxv_replay.h: mxv_replay_last_error
 struct PrioCall {   // include/mxv_prio.h: mxv_prio_last_error
     std::string error;
 };
+struct C51Call {   // include/mxv_c51.h: mxv_c51_last_error
+    std::string error;
+};
 
 namespace policy_host {
 

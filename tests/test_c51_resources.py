@@ -1,0 +1,102 @@
+"""Resource budget of gym_amd/csrc/mxv_c51.hip, guarded on the CPU (hipcc cross-compiles gfx950 without a GPU; seconds).
+
+Every kernel — c51_rows, c51_leaf, c51_tree, c51_bwd, c51_q — keeps everything in registers: no scratch, no spilled vector or scalar
+register, no AGPRs, and at least the occupancy and at most the vector registers (rounded up to the allocation granule of 8) the compiler
+reported when the kernels were written (DESIGN.md §20 records the figures).  The only LDS is the four-wave combine — 4 waves x 8 values
+x 8 bytes — in the two kernels that reduce over rows; the kernels that own a row per wave have none.  Read from the compiler's
+resource report of the code object only.  Also: the source includes the shared rule, the shared sum tree and the host checks and
+defines no copy of them, no EXP or LOG of its own, and has no read-modify-write memory operation, no assembly and no shuffle."""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+from conftest import ROOT
+from policy_host import RULE_NAMES
+from test_policy_eval_resources import HIPCC, _resources
+
+CSRC = os.path.join(ROOT, "gym_amd", "csrc")
+SRC = os.path.join(CSRC, "mxv_c51.hip")
+COMBINE_LDS = 4 * 8 * 8
+# symbol: (waves per SIMD, VGPR bound, LDS bytes) as reported at the time of the change; reported VGPRs in the comments
+BUDGET = {
+    "_ZN12_GLOBAL__N_18c51_rowsENS_7C51ArgsE": (8, 40, 0),               # 38
+    "_ZN12_GLOBAL__N_18c51_leafENS_8LeafArgsE": (8, 48, COMBINE_LDS),    # 45
+    "_ZN12_GLOBAL__N_18c51_treeENS_8TreeArgsE": (8, 48, COMBINE_LDS),    # 45
+    "_ZN12_GLOBAL__N_17c51_bwdENS_7C51ArgsE": (8, 32, 0),                # 30
+    "_ZN12_GLOBAL__N_15c51_qENS_7C51ArgsE": (8, 24, 0),                  # 22
+}
+
+
+@pytest.fixture(scope="module")
+def remarks():
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    d = tempfile.mkdtemp(prefix="mxv_c51_res_")
+    try:
+        p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-c", SRC,
+                            "-o", os.path.join(d, "k.o"), "-Rpass-analysis=kernel-resource-usage"], cwd=d, capture_output=True, text=True,
+                           timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        yield p.stderr
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def test_every_kernel_stays_in_registers_and_the_only_lds_is_the_combine(remarks):
+    res = _resources(remarks)
+    assert sorted(res) == sorted(BUDGET)
+    for kernel, (occupancy, vgprs, lds) in BUDGET.items():
+        r = res[kernel]
+        print(kernel, r)
+        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["AGPRs"] == 0, (kernel, r)
+        assert r["LDS Size"] == lds, (kernel, r)
+        assert r["Occupancy"] >= occupancy and r["VGPRs"] <= vgprs, (kernel, r)
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("## 20."):]
+    for name in ("c51_rows", "c51_leaf", "c51_tree", "c51_bwd", "c51_q"):      # the table of §20: VGPRs, SGPRs, waves / SIMD, LDS bytes
+        row = re.search(rf"\| `{name}` \| \d+ \| \d+ \| (\d+) \| (\d+) \| 0 \|", section)
+        assert row, name
+        r = next(v for k, v in res.items() if f"{name}E" in k)
+        assert (r["Occupancy"], r["LDS Size"]) == tuple(int(x) for x in row.groups()), (name, r, row.groups())
+
+
+def test_the_source_shares_the_rule_the_tree_and_the_host_checks():
+    src = re.sub(r"//.*", "", open(SRC).read())
+    for header in ("mxv_policy_rule.hpp", "mxv_policy_host.hpp", "mxv_sum_tree.hpp"):
+        assert f'#include "{header}"' in src, header
+    assert "kThreads" in src and "kMaxActions" in src
+    assert "Call<mxv::C51Call>" in src and "check_ranges(" in src and "check_stride(" in src
+    for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b",
+                 r"\bwave_tree\s*\(double", r"struct\s+(Add|Min|Max)\b", r"\bdouble\s+(exp_rule|log_rule|e_of)\b", r"\b(exp|log|expf|logf|__expf|__logf)\s*\("):
+        assert not re.search(copy, src), copy
+    assert not RULE_NAMES.search(src)      # none of the rule's constants is defined here
+    assert "e_of(" in src and "log_rule(" in src
+    # the only atomics would be on integer types: there is none at all, no assembly and no shuffle
+    for word in ("atomic", "asm", "__shfl", "#if MXV_"):
+        assert word not in src, word
+    tree = re.sub(r"//.*", "", open(os.path.join(CSRC, "mxv_sum_tree.hpp")).read())
+    for word in ("atomic", "asm", "__shfl", "#if MXV_"):
+        assert word not in tree, word
+    # one combine in each of the two kernels that reduce over rows
+    assert src.count("__shared__") == 2 and src.count("__syncthreads()") == 2
+    for script in ("build.sh", "build_asan.sh"):
+        assert "mxv_c51.hip" in open(os.path.join(CSRC, script)).read(), script
+    flags = open(os.path.join(CSRC, "build.sh")).read()
+    assert "-ffp-contract=off" in flags and "-fno-fast-math" in flags and "-ffast-math" not in flags
+    host = open(os.path.join(CSRC, "mxv_policy_host.hpp")).read()
+    assert "struct C51Call {" in host and "struct DqnCall {" in host
+
+
+def test_the_launch_constants_the_module_exports_are_the_kernels():
+    from gym_amd import c51
+
+    src = open(SRC).read()
+    rule = open(os.path.join(CSRC, "mxv_policy_rule.hpp")).read()
+    assert f"constexpr int kLeafRows = {c51.LEAF_ROWS};" in src and f"constexpr int kTreeFan = {c51.LEAF_ROWS};" in src
+    assert f"constexpr int kGridX = 1 << {c51.GRID_X.bit_length() - 1};" in src and c51.GRID_X & (c51.GRID_X - 1) == 0
+    assert "constexpr int kWaves = kThreads / 64;" in src and f"constexpr int kThreads = {64 * c51.TILE_ROWS};" in rule
+    assert f"constexpr int kMaxBlocks = {c51.MAX_BLOCKS};" in rule and f"constexpr int kMaxAtoms = {c51.MAX_ATOMS};" in src
