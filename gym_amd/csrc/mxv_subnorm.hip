@@ -89,7 +89,7 @@ __device__ __forceinline__ void store_row(double *base, int64_t row, const doubl
 // Three quotients by the SAME divisor per update (delta / tot, square(delta) * count / tot, M2 / tot): the reciprocal part of `/` runs once
 // per update and each dividend pays the three-instruction tail plus v_div_fixup (mxv_divide.hpp: div_shared, the form mxv_device.hpp uses
 // for Acrobot's shared divisor).  Operands outside the guards' range (statistics somebody injected, never the dynamics) send the WAVE down
-// the plain `/` path, so the result is IEEE division bit for bit everywhere; tests/test_gpu_subnorm.py walks both paths and
+// the plain `/` path, so the result is IEEE division bit for bit everywhere; tests/test_gpu_subnorm_edges.py walks every path and
 // tests/test_gpu_device_math.py holds div_shared to `/` wherever the guards pass, on both sides of every guard edge.
 using mxv::div_shared;
 using mxv::plain_delta;
@@ -97,12 +97,22 @@ using mxv::plain_divisor;
 using mxv::plain_operand;
 using mxv::refined_rcp;
 
+// The count the short path may take: +0.0, or positive with plain_divisor's exponent window.  The reference's M2 is m_a + m_b + ... with
+// m_b = +0.0 (:41), and that zero is not idle once the count carries a sign (injected -0.0 or -0.5, never a real run): m_a and the third
+// term are then both -0.0 and `+ 0.0` turns their sum into +0.0.  The short path drops m_b, so every negative-signed count takes the plain
+// path, which adds it.  (The exponent field with the sign left on top of it: a set sign puts it past the window; -0.0 is not all-zero bits.
+// The same count of instructions as plain_divisor(count) || count == 0.0.)
+__device__ __forceinline__ bool short_count(double c) {
+    const uint32_t e = (uint32_t)__double2hiint(c) >> 20;
+    return e - 959u < 129u || __double_as_longlong(c) == 0;
+}
+
 // RunningMeanStd.update with a batch of one row (normalize.py:17-22 -> :32-47): batch_mean = x, batch_var = 0, batch_count = 1.
 template <int D>
 __device__ __forceinline__ void update_one(const float (&x)[D], double (&mean)[D], double (&var)[D], double &count) {
     const double tot = count + 1.0;  // :37
     double delta[D], sq[D];
-    bool ok = plain_divisor(tot) && (plain_divisor(count) || count == 0.0);
+    bool ok = plain_divisor(tot) && short_count(count);
 #pragma unroll
     for (int j = 0; j < D; ++j) {
         delta[j] = (double)x[j] - mean[j];                           // :36   float32 - float64 -> float64
@@ -129,7 +139,7 @@ __device__ __forceinline__ void update_one(const float (&x)[D], double (&mean)[D
     } else {
 #pragma unroll
         for (int j = 0; j < D; ++j) {
-            const double m2 = var[j] * count + sq[j] / tot;
+            const double m2 = var[j] * count + 0.0 + sq[j] / tot;    // m_b kept: the sign of a zero M2 under a negative-signed count
             mean[j] = mean[j] + delta[j] / tot;
             var[j] = m2 / tot;
         }
@@ -232,14 +242,14 @@ __global__ void __launch_bounds__(kThreads) subnorm_rew_kernel(const SubRewArgs 
         ret = ret * a.gamma + rw;                                   // :132
         {                                                           // :144 return_rms.update(self.returns): a batch of one (update_one)
             const double tot = count + 1.0, delta = ret - mean, sq = (delta * delta) * count;
-            const bool ok = plain_divisor(tot) && (plain_divisor(count) || count == 0.0) && plain_delta(delta);
+            const bool ok = plain_divisor(tot) && short_count(count) && plain_delta(delta);
             if (__all(ok)) {
                 const double rc = refined_rcp(tot);
                 const double m2 = var * count + div_shared(sq, tot, rc);
                 mean = mean + div_shared(delta, tot, rc);
                 var = __all(plain_operand(m2)) ? div_shared(m2, tot, rc) : m2 / tot;
             } else {
-                const double m2 = var * count + sq / tot;
+                const double m2 = var * count + 0.0 + sq / tot;
                 mean = mean + delta / tot;
                 var = m2 / tot;
             }
