@@ -43,6 +43,8 @@ _LAZY = {
     "PrioritizedReplayBuffer": ("gym_amd.prioritized", "PrioritizedReplayBuffer"),
     "categorical_dqn_loss": ("gym_amd.c51", "categorical_dqn_loss"),
     "categorical_q_values": ("gym_amd.c51", "categorical_q_values"),
+    "rsample_squashed_gaussian": ("gym_amd.squashed", "rsample_squashed_gaussian"),
+    "SquashedGaussianSampler": ("gym_amd.squashed", "SquashedGaussianSampler"),
 }
 
 def __getattr__(name):

@@ -113,6 +113,22 @@ class _RolloutBase:
                              "use policy_sampler()")
         return GaussianSampler(1, seed=self.handle._action_seed if seed is None else seed, env_offset=self.env_offset, device=self.device)
 
+    def squashed_gaussian_sampler(self, seed=None):
+        """A gym_amd.squashed.SquashedGaussianSampler for this rollout's Box actions (one dim): the bounds of the env's action space
+        (Pendulum-v1 +-2, MountainCarContinuous-v0 +-1), its env_offset (so that shards of one logical vector env draw what the whole
+        would), on its device; `seed` defaults to the rollout's action_seed.  sampler.sample(mean, log_std)[0] is what step() takes,
+        sampler.rsample(mean, log_std) the differentiable draw of an off-policy update."""
+        from .registration import single_spaces
+        from .squashed import SquashedGaussianSampler
+
+        n, _ = self._policy_head
+        if n >= 1:
+            raise ValueError(f"{type(self).__name__}: squashed_gaussian_sampler() draws Box actions; this env takes Discrete({n}) "
+                             "actions: use policy_sampler()")
+        box = single_spaces(self.spec.kind)[1]
+        return SquashedGaussianSampler(int(box.shape[0]), low=box.low, high=box.high, seed=self.handle._action_seed if seed is None else seed,
+                                       env_offset=self.env_offset, device=self.device)
+
     def replay_buffer(self, capacity, seed=None):
         """A gym_amd.replay.ReplayBuffer for this rollout's transitions: its observation shape and dtype, its action dtype, on its
         device; `seed` defaults to the rollout's action_seed.  buf.add_chunk(first_obs, traj) stores what rollout_per_step /

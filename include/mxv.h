@@ -45,7 +45,8 @@
  *             g = j >> 1 and the 64-bit word made of words 2(j & 1) + 1 and 2(j & 1) for row j of sample step t: the multiply-high of that
  *             word and the tree's total descends the integer sum tree (the rule is in that header)
  *   stream tags in ctr[3] >> 28: 1 actions, 2 resets, 3 tabular transitions, 4 step noise, 5 Blackjack draws, 6 action bits, 7 policy draws,
- *             8 Gaussian policy draws, 9 replay index draws, 10 prioritised replay draws
+ *             8 Gaussian policy draws, 9 replay index draws, 10 prioritised replay draws,
+ *             11 squashed-Gaussian reparameterisation noise (an optional header of its own; tag 8's counter layout)
  * t = index of the vector step since the last mxv_seed().  Streams use GLOBAL env indices: any sharding of one logical vector env
  * over several handles / GPUs draws the same numbers.
  *
