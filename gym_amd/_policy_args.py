@@ -10,6 +10,7 @@ from . import _native
 MAX_ACTIONS = 64
 MAX_ACTION_DIM = 4                      # dims of a Gaussian head: one Philox call per env yields four normals
 STRAIGHT_LINE_ACTIONS = (2, 3, 4, 6)    # action counts with a register-resident instantiation (gym_amd/csrc/mxv_policy.hip, mxv_policy_eval.hip)
+LEAF_ROWS = 1024                        # rows per leaf of the sum tree of the losses, and partials per group of a level (kLeafRows, kTreeFan of gym_amd/csrc/mxv_sum_tree.hpp)
 _U64 = (1 << 64) - 1
 
 
@@ -85,6 +86,28 @@ def _vector(t, x, name, lead, dtypes):
     if v is None or (v.shape[0] > 1 and v.stride(0) != 1):
         raise ValueError(f"{name} must be contiguous (strides {tuple(x.stride())})")
     return v
+
+
+def _tree_launches(rows):
+    """Launches of the sum tree over `rows` rows: the leaves, then one per level of LEAF_ROWS partials a group until one group is left."""
+    count, n = -(-int(rows) // LEAF_ROWS), 2
+    while count > LEAF_ROWS:
+        count, n = -(-count // LEAF_ROWS), n + 1
+    return n
+
+
+def _workspace(t, workspace, M, dev, need, module_name):
+    """The caller's workspace (a contiguous 1-D uint8 or float64 tensor of at least `need` bytes, what gym_amd.`module_name`.workspace_bytes(M)
+    gives), or a fresh one -> (tensor, its bytes)."""
+    if workspace is None:
+        return t.empty(need // 8, dtype=t.float64, device=dev), need
+    w = _vector(t, workspace, "workspace", getattr(workspace, "shape", ()), (t.uint8, t.float64))
+    if w.dim() != 1 or tuple(workspace.shape) != tuple(w.shape):
+        raise ValueError(f"workspace must be 1-D, got shape {tuple(workspace.shape)}")
+    have = w.numel() * w.element_size()
+    if have < need:
+        raise ValueError(f"workspace holds {have} bytes, {M} rows need {need} (gym_amd.{module_name}.workspace_bytes)")
+    return w, have
 
 
 def _one_device(named):

@@ -21,8 +21,10 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native
-from ._policy_args import MAX_ACTIONS, _one_device, _ptr, _vector
+from ._policy_args import LEAF_ROWS       # rows per leaf of the sum tree, and leaves per group of a level (kLeafRows, kTreeFan)
+from ._policy_args import MAX_ACTIONS, _one_device, _ptr, _tree_launches, _vector
 from ._policy_args import _check as _raise
+from ._policy_args import _workspace as _shared_workspace
 from .dqn import _no_grad_input
 from .returns import _scalar
 
@@ -32,8 +34,7 @@ LOSS_TERM, Q_TAKEN_MEAN, TARGET_MEAN, ENTROPY_MEAN, CLIPPED_MASS_MEAN, ROW_LOSS_
 STATS = 8
 STAT_NAMES = ("loss_term", "q_taken_mean", "target_mean", "entropy_mean", "clipped_mass_mean", "row_loss_max", "q_taken_min", "q_taken_max")
 MIN_ATOMS, MAX_ATOMS = 2, 64
-# the launch shape (gym_amd/csrc/mxv_c51.hip, mxv_policy_rule.hpp)
-LEAF_ROWS = 1024        # rows per leaf of the sum tree, and leaves per group of a level (kLeafRows, kTreeFan)
+# the launch shape (gym_amd/csrc/mxv_c51.hip, mxv_policy_rule.hpp; LEAF_ROWS above: mxv_sum_tree.hpp)
 TILE_ROWS = 4           # rows (loss, backward) or (row, action) pairs (categorical_q_values) per workgroup: one per wave (kWaves)
 GRID_X = 1 << 16        # tiles along x of the grid of the rows and the backward kernels: beyond, the grid grows along y (kGridX)
 MAX_BLOCKS = 2048       # workgroups of categorical_q_values, which stride over its tiles (kMaxBlocks)
@@ -69,27 +70,11 @@ def launches(rows: int) -> int:
     """Kernel launches of one forward on `rows` rows: the rows, the leaves (which finish a batch of one leaf), then one per level of the
     tree: 2 up to 1024 rows, 3 up to 2^20, 4 up to 2^30.  The backward and categorical_q_values are always one."""
     workspace_bytes(rows)
-    count, n = -(-int(rows) // LEAF_ROWS), 2
-    if count == 1:
-        return n
-    n += 1
-    while count > LEAF_ROWS:
-        count, n = -(-count // LEAF_ROWS), n + 1
-    return n
+    return 2 if int(rows) <= LEAF_ROWS else 1 + _tree_launches(rows)
 
 
 def _workspace(t, workspace, M, dev):
-    """The caller's workspace (a contiguous 1-D uint8 or float64 tensor that is large enough), or a fresh one."""
-    need = workspace_bytes(M)
-    if workspace is None:
-        return t.empty(need // 8, dtype=t.float64, device=dev), need
-    w = _vector(t, workspace, "workspace", getattr(workspace, "shape", ()), (t.uint8, t.float64))
-    if w.dim() != 1 or tuple(workspace.shape) != tuple(w.shape):
-        raise ValueError(f"workspace must be 1-D, got shape {tuple(workspace.shape)}")
-    have = w.numel() * w.element_size()
-    if have < need:
-        raise ValueError(f"workspace holds {have} bytes, {M} rows need {need} (gym_amd.c51.workspace_bytes)")
-    return w, have
+    return _shared_workspace(t, workspace, M, dev, workspace_bytes(M), "c51")
 
 
 def _heads(t, x, name):

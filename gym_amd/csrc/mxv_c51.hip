@@ -38,8 +38,6 @@ using namespace mxv::policy_host;
 using namespace mxv::sum_tree;
 
 constexpr int kWaves = kThreads / 64;    // rows per tile of c51_rows, c51_bwd and c51_q: one per wave
-constexpr int kLeafRows = 1024;          // rows per leaf: four per lane
-constexpr int kTreeFan = 1024;           // partials folded per workgroup per tree level: four per lane
 constexpr int kV = MXV_C51_STATS;        // partials of a leaf: sums of term, qa, y, ent, cm; max ce, min qa, max qa
 constexpr int kCols = 6;                 // columns a row leaves in the workspace: term, qa, y, ent, cm, ce
 constexpr int kMaxAtoms = 64;
@@ -201,31 +199,30 @@ __global__ void __launch_bounds__(kThreads) c51_rows(const C51Args p) {
 }
 
 // ---- forward: the leaves and the tree ----
-template <class Op>
-__device__ __forceinline__ double fold(const double (*sm)[kV], int v) { return four_waves<Op, kV>(sm, v); }
-
-// the operation of partial v
-__device__ __forceinline__ double combine(const double (*sm)[kV], int v) {
-    return v == MXV_C51_Q_TAKEN_MIN ? fold<Min>(sm, v) : (v == MXV_C51_ROW_LOSS_MAX || v == MXV_C51_Q_TAKEN_MAX) ? fold<Max>(sm, v) : fold<Add>(sm, v);
-}
+// which of a leaf's partials is a minimum, which a maximum; the others are sums
+struct Partials {
+    static constexpr int V = kV;
+    static constexpr bool is_min(int v) { return v == MXV_C51_Q_TAKEN_MIN; }
+    static constexpr bool is_max(int v) { return v == MXV_C51_ROW_LOSS_MAX || v == MXV_C51_Q_TAKEN_MAX; }
+};
 
 // the first lane writes the loss and the diagnostics from the last group's four waves
 __device__ __forceinline__ void finish(const double (*sm)[kV], int64_t M, float *loss_out, float *stats) {
     const double Mf = (double)M;
-    const double loss = fold<Add>(sm, MXV_C51_LOSS_TERM) / Mf;
+    const double loss = four_waves<Add>(sm, MXV_C51_LOSS_TERM) / Mf;
     loss_out[0] = to_f32(loss);
     stats[MXV_C51_LOSS_TERM] = to_f32(loss);
-    stats[MXV_C51_Q_TAKEN_MEAN] = to_f32(fold<Add>(sm, MXV_C51_Q_TAKEN_MEAN) / Mf);
-    stats[MXV_C51_TARGET_MEAN] = to_f32(fold<Add>(sm, MXV_C51_TARGET_MEAN) / Mf);
-    stats[MXV_C51_ENTROPY_MEAN] = to_f32(fold<Add>(sm, MXV_C51_ENTROPY_MEAN) / Mf);
-    stats[MXV_C51_CLIPPED_MASS_MEAN] = to_f32(fold<Add>(sm, MXV_C51_CLIPPED_MASS_MEAN) / Mf);
-    stats[MXV_C51_ROW_LOSS_MAX] = to_f32(fold<Max>(sm, MXV_C51_ROW_LOSS_MAX) + 0.0);      // + 0.0: a zero of either sign leaves as +0.0
-    stats[MXV_C51_Q_TAKEN_MIN] = to_f32(fold<Min>(sm, MXV_C51_Q_TAKEN_MIN) + 0.0);
-    stats[MXV_C51_Q_TAKEN_MAX] = to_f32(fold<Max>(sm, MXV_C51_Q_TAKEN_MAX) + 0.0);
+    stats[MXV_C51_Q_TAKEN_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_Q_TAKEN_MEAN) / Mf);
+    stats[MXV_C51_TARGET_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_TARGET_MEAN) / Mf);
+    stats[MXV_C51_ENTROPY_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_ENTROPY_MEAN) / Mf);
+    stats[MXV_C51_CLIPPED_MASS_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_CLIPPED_MASS_MEAN) / Mf);
+    stats[MXV_C51_ROW_LOSS_MAX] = to_f32(four_waves<Max>(sm, MXV_C51_ROW_LOSS_MAX) + 0.0);      // + 0.0: a zero of either sign leaves as +0.0
+    stats[MXV_C51_Q_TAKEN_MIN] = to_f32(four_waves<Min>(sm, MXV_C51_Q_TAKEN_MIN) + 0.0);
+    stats[MXV_C51_Q_TAKEN_MAX] = to_f32(four_waves<Max>(sm, MXV_C51_Q_TAKEN_MAX) + 0.0);
 }
 
 __global__ void __launch_bounds__(kThreads) c51_leaf(const LeafArgs a) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
     double s = 0.0, sq = 0.0, sy = 0.0, se = 0.0, sc = 0.0, mx_ce = Max::identity(), mn_q = Min::identity(), mx_q = Max::identity();
 #pragma unroll
@@ -248,42 +245,22 @@ __global__ void __launch_bounds__(kThreads) c51_leaf(const LeafArgs a) {
     const double zero = a.last ? 0.0 : -0.0;
     const double t[kV] = {wave_tree<Add>(s) + zero,  wave_tree<Add>(sq) + zero, wave_tree<Add>(sy) + zero, wave_tree<Add>(se) + zero,
                           wave_tree<Add>(sc) + zero, wave_tree<Max>(mx_ce),     wave_tree<Min>(mn_q),      wave_tree<Max>(mx_q)};
-    if (lane == 0) {
-#pragma unroll
-        for (int v = 0; v < kV; ++v) sm[wave][v] = t[v];
-    }
-    __syncthreads();
+    leave_wave_values(sm, t);
     if (!a.last) {
-        if (tid < kV) a.partials[(int64_t)blockIdx.x * kV + tid] = combine(sm, tid);
+        write_partials<Partials>(sm, a.partials);
         return;
     }
     if (tid == 0) finish(sm, a.M, a.loss, a.stats);
 }
 
-template <class Op>
-__device__ __forceinline__ double group_value(const TreeArgs &t, int64_t l0, int v) {
-    double a[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = l0 + i < t.count ? t.in[(l0 + i) * kV + v] : Op::identity();
-    return wave_tree<Op>(Op::op(Op::op(a[0], a[1]), Op::op(a[2], a[3])));
-}
-
 __global__ void __launch_bounds__(kThreads) c51_tree(const TreeArgs t) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t l0 = (int64_t)blockIdx.x * kTreeFan + (int64_t)tid * 4;
     __shared__ double sm[kThreads / 64][kV];
-#pragma unroll
-    for (int v = 0; v < kV; ++v) {
-        const double x = v == MXV_C51_Q_TAKEN_MIN ? group_value<Min>(t, l0, v)
-                         : (v == MXV_C51_ROW_LOSS_MAX || v == MXV_C51_Q_TAKEN_MAX) ? group_value<Max>(t, l0, v) : group_value<Add>(t, l0, v);
-        if (lane == 0) sm[wave][v] = x;
-    }
-    __syncthreads();
+    fold_level<Partials>(sm, t.in, t.count);
     if (!t.last) {
-        if (tid < kV) t.out[(int64_t)blockIdx.x * kV + tid] = combine(sm, tid);
+        write_partials<Partials>(sm, t.out);
         return;
     }
-    if (tid == 0) finish(sm, t.M, t.loss, t.stats);
+    if (threadIdx.x == 0) finish(sm, t.M, t.loss, t.stats);
 }
 
 // ---- backward ----
@@ -321,17 +298,8 @@ __global__ void __launch_bounds__(kThreads) c51_q(const C51Args p) {
 }
 
 // ---- host ----
-int64_t leaves_of(int64_t M) { return (M + kLeafRows - 1) / kLeafRows; }
-
 // doubles of workspace: the six columns of the rows, the leaves' partials, and every level of the tree that is not the last
-int64_t workspace_doubles(int64_t M) {
-    int64_t count = leaves_of(M), slots = count;
-    while (count > kTreeFan) {
-        count = (count + kTreeFan - 1) / kTreeFan;
-        slots += count;
-    }
-    return kCols * M + slots * kV;
-}
+int64_t workspace_doubles(int64_t M) { return kCols * M + workspace_slots(M) * kV; }
 
 using CCall = Call<mxv::C51Call>;
 
@@ -417,18 +385,6 @@ int launch_rows(const CCall &call, const void *kernel, C51Args &a, void *stream)
     return e == hipSuccess ? MXV_OK : call.hip_failed("kernel launch", e);
 }
 
-int run_tree(const CCall &call, TreeArgs t, double *ws, int64_t leaves, void *stream) {
-    int64_t count = leaves, offset = leaves * kV;
-    const double *in = ws;
-    for (;;) {
-        const int64_t groups = (count + kTreeFan - 1) / kTreeFan;
-        t.in = in; t.count = count; t.last = groups == 1; t.out = t.last ? nullptr : ws + offset;
-        if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&c51_tree), t, groups, stream)) return rc;
-        if (t.last) return MXV_OK;
-        in = t.out; offset += groups * kV; count = groups;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -447,10 +403,8 @@ int mxv_c51_loss(void *stream, int64_t M, int32_t A, int32_t Z, const float *log
         return rc;
     if (!loss_out_dev) return call.bad("%s: loss_out pointer is NULL", call.api);
     if (!stats_out_dev) return call.bad("%s: stats_out pointer is NULL", call.api);
-    if (!workspace_dev) return call.bad("%s: workspace pointer is NULL", call.api);
     const int64_t need = mxv_c51_workspace_bytes(M);
-    if (workspace_bytes < need)
-        return call.bad("%s: workspace_bytes = %lld is below mxv_c51_workspace_bytes(%lld) = %lld", call.api, (long long)workspace_bytes, (long long)M, (long long)need);
+    if (int rc = check_workspace(call, "mxv_c51_workspace_bytes", M, workspace_dev, workspace_bytes, need)) return rc;
     Range ins[kInputs];
     input_ranges(p, nullptr, ins);
     const Range outs[] = {{"workspace", (uintptr_t)workspace_dev, (uint64_t)need, 8},
@@ -470,7 +424,7 @@ int mxv_c51_loss(void *stream, int64_t M, int32_t A, int32_t Z, const float *log
     if (l.last) return MXV_OK;
     TreeArgs t{};
     t.M = M; t.loss = loss_out_dev; t.stats = stats_out_dev;
-    return run_tree(call, t, l.partials, leaves, stream);
+    return run_tree(call, reinterpret_cast<const void *>(&c51_tree), kV, t, l.partials, leaves, stream);
 }
 
 int mxv_c51_loss_backward(void *stream, int64_t M, int32_t A, int32_t Z, const float *logits_dev, int64_t logits_ld, const void *actions_dev,

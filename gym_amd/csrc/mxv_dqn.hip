@@ -2,7 +2,7 @@
 // TD errors, its diagnostics and its dense gradient with respect to q (include/mxv_dqn.h).
 //
 // The results are defined bit for bit by the rule in the header: float64, one rounding per operation (this file is built with
-// -ffp-contract=off like the rest of the library), and every sum the fixed tree of mxv_ppo.hip over the row index — nothing here depends
+// -ffp-contract=off like the rest of the library), and every sum the fixed tree of mxv_sum_tree.hpp over the row index — nothing here depends
 // on the order in which lanes or workgroups arrive.  The argument checks are those of mxv_policy_host.hpp.
 //
 // Shape of the kernels (about 12 fp64 operations for 25 + 4 A bytes a row forwards, 8 for 21 + 8 A backwards: bound by memory):
@@ -19,8 +19,7 @@
 //     tile's 256 A consecutive floats with lane t taking elements t, t + 256, ...: every wave store is a dense burst of 64 dwords,
 //     whatever A is.
 //   * everything in the rule is a select; which optional inputs there are is a uniform branch.
-//   * wave_tree / four_waves are a copy of mxv_ppo.hip's (that file's text is pinned by its resource test); DESIGN.md §17 names the
-//     shared header as deferred work.
+//   * the tree — butterfly, four waves, levels, workspace — is mxv_sum_tree.hpp's; here are the rows, the leaf's sums and the finish.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,14 +29,14 @@
 #include "../../include/mxv_dqn.h"
 #include "mxv_policy_host.hpp"
 #include "mxv_policy_rule.hpp"
+#include "mxv_sum_tree.hpp"
 
 namespace {
 
 using namespace mxv::rule;
 using namespace mxv::policy_host;
+using namespace mxv::sum_tree;
 
-constexpr int kLeafRows = 1024;      // rows per leaf: four per lane
-constexpr int kTreeFan = 1024;       // partials folded per workgroup per tree level: four per lane
 constexpr int kV = MXV_DQN_STATS;    // partials of a leaf: sums of term, ae, qa, y, lin; max ae, min qa, max qa
 
 struct DqnArgs {
@@ -61,65 +60,12 @@ struct TreeArgs {
     float *loss, *stats;
 };
 
-__device__ __forceinline__ double nan64() { return __longlong_as_double(0x7FF8000000000000ll); }
-// round to nearest even; every NaN leaves as the one pattern
-__device__ __forceinline__ float to_f32(double x) {
-    const float y = (float)x;
-    return y != y ? __uint_as_float(0x7FC00000u) : y;
-}
-
-struct Add {
-    static __device__ __forceinline__ double identity() { return 0.0; }
-    static __device__ __forceinline__ double op(double a, double b) { return a + b; }
+// which of a leaf's partials is a minimum, which a maximum; the others are sums
+struct Partials {
+    static constexpr int V = kV;
+    static constexpr bool is_min(int v) { return v == MXV_DQN_Q_TAKEN_MIN; }
+    static constexpr bool is_max(int v) { return v == MXV_DQN_TD_ABS_MAX || v == MXV_DQN_Q_TAKEN_MAX; }
 };
-struct Min {   // operands are never NaN (a NaN is skipped at its row); two zeros of either sign are one value: the finish writes +0.0
-    static __device__ __forceinline__ double identity() { return (double)__builtin_inff(); }
-    static __device__ __forceinline__ double op(double a, double b) { return b < a ? b : a; }
-};
-struct Max {
-    static __device__ __forceinline__ double identity() { return -(double)__builtin_inff(); }
-    static __device__ __forceinline__ double op(double a, double b) { return b > a ? b : a; }
-};
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-// The xor butterfly over lane bits 0..5 = the pairwise tree over the lane index of a wave; every lane ends with the tree's value.
-// Stages 1, 2: quad permutes.  Stages 4, 8: after them every lane of a quad (of a half row) holds the same partial, so the mirror
-// permutes deliver what lane ^ 4 (lane ^ 8) holds.  Stages 16, 32: v_permlane16_swap / v_permlane32_swap.  Op commutes, so the value
-// is that of the lane ^ (1 << b) form of the rule.
-template <class Op>
-__device__ __forceinline__ double wave_tree(double v) {
-    v = Op::op(v, dpp_f64<0xB1>(v));     // quad_perm [1, 0, 3, 2]
-    v = Op::op(v, dpp_f64<0x4E>(v));     // quad_perm [2, 3, 0, 1]
-    v = Op::op(v, dpp_f64<0x141>(v));    // row_half_mirror
-    v = Op::op(v, dpp_f64<0x140>(v));    // row_mirror
-    {
-        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = Op::op(__hiloint2double((int)b[0], (int)a[0]), __hiloint2double((int)b[1], (int)a[1]));   // rows (0, 1), (2, 3)
-    }
-    {
-        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = Op::op(__hiloint2double((int)b[0], (int)a[0]), __hiloint2double((int)b[1], (int)a[1]));   // lower half, upper half
-    }
-    return v;
-}
-
-template <class Op>
-__device__ __forceinline__ double four_waves(const double (*sm)[kV], int v) {
-    return Op::op(Op::op(sm[0][v], sm[1][v]), Op::op(sm[2][v], sm[3][v]));
-}
-
-// the operation of partial v
-__device__ __forceinline__ double combine(const double (*sm)[kV], int v) {
-    return v == MXV_DQN_Q_TAKEN_MIN ? four_waves<Min>(sm, v) : (v == MXV_DQN_TD_ABS_MAX || v == MXV_DQN_Q_TAKEN_MAX) ? four_waves<Max>(sm, v) : four_waves<Add>(sm, v);
-}
 
 // ---- one row of the rule ----
 struct Row {
@@ -197,7 +143,7 @@ __device__ __forceinline__ Row row_of(const DqnArgs &p, int64_t i) {
 // ---- forward: the leaves ----
 template <int AT>
 __global__ void __launch_bounds__(kThreads) dqn_leaf(const DqnArgs p) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
     const bool has_w = p.weights != nullptr;      // uniform
     double s = 0.0, sa = 0.0, sq = 0.0, sy = 0.0, sl = 0.0, mx_ae = Max::identity(), mn_q = Min::identity(), mx_q = Max::identity();
@@ -220,39 +166,19 @@ __global__ void __launch_bounds__(kThreads) dqn_leaf(const DqnArgs p) {
     __shared__ double sm[kThreads / 64][kV];
     const double t[kV] = {wave_tree<Add>(s), wave_tree<Add>(sa), wave_tree<Add>(sq), wave_tree<Add>(sy),
                           wave_tree<Add>(sl), wave_tree<Max>(mx_ae), wave_tree<Min>(mn_q), wave_tree<Max>(mx_q)};
-    if (lane == 0) {
-#pragma unroll
-        for (int v = 0; v < kV; ++v) sm[wave][v] = t[v];
-    }
-    __syncthreads();
-    if (tid < kV) p.partials[(int64_t)blockIdx.x * kV + tid] = combine(sm, tid);
+    leave_wave_values(sm, t);
+    write_partials<Partials>(sm, p.partials);
 }
 
 // ---- forward: one level of the tree; the last one finishes ----
-template <class Op>
-__device__ __forceinline__ double group_value(const TreeArgs &t, int64_t l0, int v) {
-    double a[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = l0 + i < t.count ? t.in[(l0 + i) * kV + v] : Op::identity();
-    return wave_tree<Op>(Op::op(Op::op(a[0], a[1]), Op::op(a[2], a[3])));
-}
-
 __global__ void __launch_bounds__(kThreads) dqn_tree(const TreeArgs t) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t l0 = (int64_t)blockIdx.x * kTreeFan + (int64_t)tid * 4;
     __shared__ double sm[kThreads / 64][kV];
-#pragma unroll
-    for (int v = 0; v < kV; ++v) {
-        const double x = v == MXV_DQN_Q_TAKEN_MIN ? group_value<Min>(t, l0, v)
-                         : (v == MXV_DQN_TD_ABS_MAX || v == MXV_DQN_Q_TAKEN_MAX) ? group_value<Max>(t, l0, v) : group_value<Add>(t, l0, v);
-        if (lane == 0) sm[wave][v] = x;
-    }
-    __syncthreads();
+    fold_level<Partials>(sm, t.in, t.count);
     if (!t.last) {
-        if (tid < kV) t.out[(int64_t)blockIdx.x * kV + tid] = combine(sm, tid);
+        write_partials<Partials>(sm, t.out);
         return;
     }
-    if (tid != 0) return;
+    if (threadIdx.x != 0) return;
     const double Mf = (double)t.M;
     const double loss = four_waves<Add>(sm, MXV_DQN_LOSS_TERM) / Mf;
     t.loss[0] = to_f32(loss);
@@ -318,18 +244,6 @@ __global__ void __launch_bounds__(kThreads) dqn_bwd(const DqnArgs p) {
 }
 
 // ---- host ----
-int64_t leaves_of(int64_t M) { return (M + kLeafRows - 1) / kLeafRows; }
-
-// doubles of workspace per value of a leaf: the leaves, and every level of the tree that is not the last
-int64_t workspace_slots(int64_t M) {
-    int64_t count = leaves_of(M), slots = count;
-    while (count > kTreeFan) {
-        count = (count + kTreeFan - 1) / kTreeFan;
-        slots += count;
-    }
-    return slots;
-}
-
 using DCall = Call<mxv::DqnCall>;
 
 template <int AT> struct Leaf { static const void *ptr() { return reinterpret_cast<const void *>(&dqn_leaf<AT>); } };
@@ -398,18 +312,6 @@ void input_ranges(const DqnArgs &p, const float *g, Range *r) {
     r[8] = {"grad_loss", (uintptr_t)g, 4, 4};
 }
 
-int run_tree(const DCall &call, TreeArgs t, double *ws, int64_t leaves, void *stream) {
-    int64_t count = leaves, offset = leaves * kV;
-    const double *in = ws;
-    for (;;) {
-        const int64_t groups = (count + kTreeFan - 1) / kTreeFan;
-        t.in = in; t.count = count; t.last = groups == 1; t.out = t.last ? nullptr : ws + offset;
-        if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&dqn_tree), t, groups, stream)) return rc;
-        if (t.last) return MXV_OK;
-        in = t.out; offset += groups * kV; count = groups;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -427,10 +329,8 @@ int mxv_dqn_loss(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t
         return rc;
     if (!loss_out_dev) return call.bad("%s: loss_out pointer is NULL", call.api);
     if (!stats_out_dev) return call.bad("%s: stats_out pointer is NULL", call.api);
-    if (!workspace_dev) return call.bad("%s: workspace pointer is NULL", call.api);
     const int64_t need = mxv_dqn_workspace_bytes(M);
-    if (workspace_bytes < need)
-        return call.bad("%s: workspace_bytes = %lld is below mxv_dqn_workspace_bytes(%lld) = %lld", call.api, (long long)workspace_bytes, (long long)M, (long long)need);
+    if (int rc = check_workspace(call, "mxv_dqn_workspace_bytes", M, workspace_dev, workspace_bytes, need)) return rc;
     Range ins[kInputs];
     input_ranges(p, nullptr, ins);
     const Range outs[] = {{"workspace", (uintptr_t)workspace_dev, (uint64_t)need, 8}, {"td_error", (uintptr_t)td_error_dev, (uint64_t)M * 4, 4},
@@ -442,7 +342,7 @@ int mxv_dqn_loss(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t
     if (int rc = call.launch_blocks(pick<Leaf>(A), p, leaves, stream)) return rc;
     TreeArgs t{};
     t.M = M; t.loss = loss_out_dev; t.stats = stats_out_dev;
-    return run_tree(call, t, p.partials, leaves, stream);
+    return run_tree(call, reinterpret_cast<const void *>(&dqn_tree), kV, t, p.partials, leaves, stream);
 }
 
 int mxv_dqn_loss_backward(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t q_ld, const void *actions_dev, int32_t action_bytes,

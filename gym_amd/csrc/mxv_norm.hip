@@ -38,48 +38,25 @@
 
 #include "../../include/mxv.h"
 #include "mxv_host.hpp"
+#include "mxv_sum_tree.hpp"
 
 using mxv::check_aligned;
 using mxv::fail;
 using mxv::last_error;
+using mxv::sum_tree::Add;
+using mxv::sum_tree::four_partials;
+using mxv::sum_tree::four_waves;
+using mxv::sum_tree::kTreeFan;
+using mxv::sum_tree::wave_tree;
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kObsLeafRows = 4096;  // rows of observations per leaf of the sum tree
 constexpr int kRewLeafEnvs = 256;   // envs per leaf of the return-sum tree (one wave64, 4 envs per lane)
-constexpr int kTreeFan = 1024;      // leaves folded per workgroup per tree level (a complete 10-level subtree)
 constexpr int kMaxWorld = 64;
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_tree_sum(double v) {
-    // xor butterfly = the binary tree over lane index (addition is commutative, so every lane holds the tree's value), without LDS round
-    // trips (__shfl_xor's six ds_bpermute stages: slower, profiles/r4/r4n_normalize_variants.txt).  Stages 1, 2: quad permutes (lane ^ 1,
-    // lane ^ 2).  Stages 4, 8: after them every lane of a quad (of a half row) holds the same partial sum, so the mirror permutes of the
-    // DPP unit — lane 7 - i of the half row, lane 15 - i of the row — deliver what lane ^ 4 (lane ^ 8) holds.  Stages 16, 32: gfx950's
-    // v_permlane16_swap / v_permlane32_swap.  a + b == b + a exactly, so the value is the __shfl_xor butterfly's, bit for bit.
-    v += dpp_f64<0xB1>(v);    // quad_perm [1, 0, 3, 2]
-    v += dpp_f64<0x4E>(v);    // quad_perm [2, 3, 0, 1]
-    v += dpp_f64<0x141>(v);   // row_half_mirror
-    v += dpp_f64<0x140>(v);   // row_mirror
-    {
-        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);   // rows (0, 1), (2, 3)
-    }
-    {
-        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);   // lower half + upper half
-    }
-    return v;
-}
+// the sum of a wave is wave_tree<Add>, the xor butterfly of mxv_sum_tree.hpp (its comment: the stages, and why DPP / permlane and not
+// __shfl_xor); a level folds kTreeFan = 1024 leaves per workgroup (a complete 10-level subtree) with the same four_partials / four_waves
 
 template <int O>
 __device__ __forceinline__ void load_row(const float *__restrict__ p, float (&f)[O]) {
@@ -128,7 +105,7 @@ __global__ void __launch_bounds__(kThreads) obs_sums_kernel(const float *__restr
     const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
     for (int j = 0; j < O; ++j) {
-        const double a = wave_tree_sum(s[j]), b = wave_tree_sum(q[j]);
+        const double a = wave_tree<Add>(s[j]), b = wave_tree<Add>(q[j]);
         if (lane == 0) {
             sm[wave][j] = a;
             sm[wave][O + j] = b;
@@ -136,7 +113,7 @@ __global__ void __launch_bounds__(kThreads) obs_sums_kernel(const float *__restr
     }
     __syncthreads();
     if (tid < 2 * O)
-        partials[(k * leaves + leaf) * (2 * O) + tid] = (sm[0][tid] + sm[1][tid]) + (sm[2][tid] + sm[3][tid]);
+        partials[(k * leaves + leaf) * (2 * O) + tid] = four_waves<Add>(sm, tid);
 }
 
 // ---- 1b. rewards: discounted-return recurrence + per-(step, leaf) sums ----------------------------------------------
@@ -218,8 +195,8 @@ __global__ void __launch_bounds__(64) returns_sums_kernel(const RT *__restrict__
                     q = __fma_rn(ret[j], ret[j], q);
                 }
             }
-            s = wave_tree_sum(s);
-            q = wave_tree_sum(q);
+            s = wave_tree<Add>(s);
+            q = wave_tree<Add>(q);
             if (lane == 0) {
                 partials[((int64_t)k * leaves + leaf) * 2 + 0] = s;
                 partials[((int64_t)k * leaves + leaf) * 2 + 1] = q;
@@ -268,12 +245,12 @@ __global__ void __launch_bounds__(kThreads) tree_kernel(const double *__restrict
             double a[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[i] = (l0 + i < leaves) ? in[(k * leaves + l0 + i) * V + v] : 0.0;
-            const double t = wave_tree_sum((a[0] + a[1]) + (a[2] + a[3]));
+            const double t = wave_tree<Add>(four_partials<Add>(a));
             if (lane == 0) sm[wave][v] = t;
         }
     }
     __syncthreads();
-    if (tid < V) out[(k * groups + group) * V + tid] = (sm[0][tid] + sm[1][tid]) + (sm[2][tid] + sm[3][tid]);
+    if (tid < V) out[(k * groups + group) * V + tid] = four_waves<Add>(sm, tid);
 }
 
 // ---- 3. the running update, sequential over the K steps (normalize.py:17-47) ------------------------------------------

@@ -131,7 +131,8 @@ struct Call {
         return e == hipSuccess ? MXV_OK : hip_failed("kernel launch", e);
     }
 
-    // `kernel`(a) on `stream` with one workgroup per leaf of a sum tree (mxv_ppo.hip): `blocks` workgroups, no striding
+    // `kernel`(a) on `stream` with one workgroup per leaf, or per group of a level, of a sum tree (mxv_sum_tree.hpp, whose run_tree
+    // launches the levels through this): `blocks` workgroups, no striding
     template <typename Args>
     int launch_blocks(const void *kernel, Args &a, int64_t blocks, void *stream) const {
         void *args[] = {&a};

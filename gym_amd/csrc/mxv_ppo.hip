@@ -2,14 +2,14 @@
 // normalised with (include/mxv_ppo.h).
 //
 // The results are defined bit for bit by the rule in the header: float64, one rounding per operation (this file is built with
-// -ffp-contract=off like the rest of the library), EXP the text of mxv_policy_rule.hpp, IEEE `/` and sqrt, and every sum a fixed tree
-// over the row index — no atomics: a float atomic would make a sum depend on the order of arrival.  The argument checks are those of
+// -ffp-contract=off like the rest of the library), EXP the text of mxv_policy_rule.hpp, IEEE `/` and sqrt, and every sum the fixed tree
+// of mxv_sum_tree.hpp over the row index — no atomics: a float atomic would make a sum depend on the order of arrival.  The argument checks are those of
 // mxv_policy_host.hpp.
 //
 // Shape of the kernels (~40 fp64 operations for 12-24 bytes a row):
 //   * ppo_leaf / moments_leaf: one workgroup of 256 lanes per leaf of 1024 consecutive rows; lane t takes rows t, t + 256, t + 512,
-//     t + 768 — every wave load is a dense burst of 64 dwords — then the xor butterfly of each wave (the DPP / permlane form of
-//     mxv_norm.hip: no LDS round trips) and the four waves through LDS, the only LDS there is: 4 x 8 doubles.  One leaf writes its
+//     t + 768 — every wave load is a dense burst of 64 dwords — then the xor butterfly of each wave (DPP / permlane:
+//     no LDS round trips) and the four waves through LDS, the only LDS there is: 4 x 8 doubles.  One leaf writes its
 //     8 (2) partials to the workspace.
 //   * ppo_tree: one workgroup per group of 1024 partials; the last level (one group) also finishes the loss and the diagnostics (the
 //     moments) in its first lane.  So a forward is 2 launches up to 2^20 rows, 3 up to 2^30.
@@ -25,14 +25,14 @@
 #include "../../include/mxv_ppo.h"
 #include "mxv_policy_host.hpp"
 #include "mxv_policy_rule.hpp"
+#include "mxv_sum_tree.hpp"
 
 namespace {
 
 using namespace mxv::rule;
 using namespace mxv::policy_host;
+using namespace mxv::sum_tree;
 
-constexpr int kLeafRows = 1024;      // rows per leaf: four per lane
-constexpr int kTreeFan = 1024;       // partials folded per workgroup per tree level: four per lane
 constexpr int kLossV = MXV_PPO_STATS, kMomentsV = 2;
 constexpr double kRatioLogMax = 80.0;
 
@@ -62,61 +62,16 @@ struct TreeArgs {
     double *moments;                 // the last level of the moments
 };
 
-__device__ __forceinline__ double nan64() { return __longlong_as_double(0x7FF8000000000000ll); }
 __device__ __forceinline__ double canonical(double x) { return x != x ? nan64() : x; }
-// round to nearest even; every NaN leaves as the one pattern
-__device__ __forceinline__ float to_f32(double x) {
-    const float y = (float)x;
-    return y != y ? __uint_as_float(0x7FC00000u) : y;
-}
 
-struct Add {
-    static __device__ __forceinline__ double identity() { return 0.0; }
-    static __device__ __forceinline__ double op(double a, double b) { return a + b; }
+// the N partials of a leaf of the loss (N = 8: the ratio's minimum and maximum are not sums) or of the moments (N = 2: both are sums).
+// A ratio is never NaN here (a NaN ratio is skipped at its row) and never zero: the selects commute.
+template <int N>
+struct Partials {
+    static constexpr int V = N;
+    static constexpr bool is_min(int v) { return v == MXV_PPO_RATIO_MIN; }
+    static constexpr bool is_max(int v) { return v == MXV_PPO_RATIO_MAX; }
 };
-struct Min {   // operands are never NaN (a NaN ratio is skipped at its row) and never zero: the select commutes
-    static __device__ __forceinline__ double identity() { return (double)__builtin_inff(); }
-    static __device__ __forceinline__ double op(double a, double b) { return b < a ? b : a; }
-};
-struct Max {
-    static __device__ __forceinline__ double identity() { return -(double)__builtin_inff(); }
-    static __device__ __forceinline__ double op(double a, double b) { return b > a ? b : a; }
-};
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-// The xor butterfly over lane bits 0..5 = the pairwise tree over the lane index of a wave; every lane ends with the tree's value.
-// Stages 1, 2: quad permutes.  Stages 4, 8: after them every lane of a quad (of a half row) holds the same partial, so the mirror
-// permutes deliver what lane ^ 4 (lane ^ 8) holds.  Stages 16, 32: v_permlane16_swap / v_permlane32_swap.  Op commutes exactly, so the
-// value is that of the lane ^ (1 << b) form of the rule, bit for bit.
-template <class Op>
-__device__ __forceinline__ double wave_tree(double v) {
-    v = Op::op(v, dpp_f64<0xB1>(v));     // quad_perm [1, 0, 3, 2]
-    v = Op::op(v, dpp_f64<0x4E>(v));     // quad_perm [2, 3, 0, 1]
-    v = Op::op(v, dpp_f64<0x141>(v));    // row_half_mirror
-    v = Op::op(v, dpp_f64<0x140>(v));    // row_mirror
-    {
-        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = Op::op(__hiloint2double((int)b[0], (int)a[0]), __hiloint2double((int)b[1], (int)a[1]));   // rows (0, 1), (2, 3)
-    }
-    {
-        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = Op::op(__hiloint2double((int)b[0], (int)a[0]), __hiloint2double((int)b[1], (int)a[1]));   // lower half, upper half
-    }
-    return v;
-}
-
-template <class Op>
-__device__ __forceinline__ double four_waves(const double (*sm)[kLossV], int v) {
-    return Op::op(Op::op(sm[0][v], sm[1][v]), Op::op(sm[2][v], sm[3][v]));
-}
 
 // ---- one row of the rule ----
 struct Row {
@@ -145,7 +100,7 @@ __device__ __forceinline__ Row row_of(const PpoArgs &p, int64_t i, bool has_m, d
 
 // ---- forward: the leaves ----
 __global__ void __launch_bounds__(kThreads) ppo_leaf(const PpoArgs p) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
     const bool has_m = p.moments != nullptr, has_ent = p.ent != nullptr, has_val = p.val != nullptr;      // uniform
     const double mean = has_m ? p.moments[0] : 0.0, inv = has_m ? p.moments[1] : 0.0;
@@ -170,19 +125,12 @@ __global__ void __launch_bounds__(kThreads) ppo_leaf(const PpoArgs p) {
     __shared__ double sm[kThreads / 64][kLossV];
     const double t[kLossV] = {wave_tree<Add>(s), has_val ? wave_tree<Add>(v2) : 0.0, has_ent ? wave_tree<Add>(en) : 0.0, wave_tree<Add>(k1),
                               wave_tree<Add>(k3), wave_tree<Add>(cf), wave_tree<Min>(mn), wave_tree<Max>(mx)};
-    if (lane == 0) {
-#pragma unroll
-        for (int v = 0; v < kLossV; ++v) sm[wave][v] = t[v];
-    }
-    __syncthreads();
-    if (tid < kLossV) {
-        const double total = tid == MXV_PPO_RATIO_MIN ? four_waves<Min>(sm, tid) : tid == MXV_PPO_RATIO_MAX ? four_waves<Max>(sm, tid) : four_waves<Add>(sm, tid);
-        p.partials[(int64_t)blockIdx.x * kLossV + tid] = total;
-    }
+    leave_wave_values(sm, t);
+    write_partials<Partials<kLossV>>(sm, p.partials);
 }
 
 __global__ void __launch_bounds__(kThreads) moments_leaf(const MomentsArgs p) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
     double s = 0.0, q = 0.0;
 #pragma unroll
@@ -194,44 +142,22 @@ __global__ void __launch_bounds__(kThreads) moments_leaf(const MomentsArgs p) {
         q = q + x * x;      // the product is exact: 24-bit significands
     }
     __shared__ double sm[kThreads / 64][kLossV];
-    const double ts = wave_tree<Add>(s), tq = wave_tree<Add>(q);
-    if (lane == 0) {
-        sm[wave][0] = ts;
-        sm[wave][1] = tq;
-    }
-    __syncthreads();
-    if (tid < kMomentsV) p.partials[(int64_t)blockIdx.x * kMomentsV + tid] = four_waves<Add>(sm, tid);
+    const double t[kMomentsV] = {wave_tree<Add>(s), wave_tree<Add>(q)};
+    leave_wave_values(sm, t);
+    write_partials<Partials<kMomentsV>>(sm, p.partials);
 }
 
 // ---- forward: one level of the tree; the last one finishes ----
-template <class Op, int V>
-__device__ __forceinline__ double group_value(const TreeArgs &t, int64_t l0, int v) {
-    double a[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = l0 + i < t.count ? t.in[(l0 + i) * V + v] : Op::identity();
-    return wave_tree<Op>(Op::op(Op::op(a[0], a[1]), Op::op(a[2], a[3])));
-}
-
 template <bool LOSS>
 __global__ void __launch_bounds__(kThreads) ppo_tree(const TreeArgs t) {
-    constexpr int V = LOSS ? kLossV : kMomentsV;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t l0 = (int64_t)blockIdx.x * kTreeFan + (int64_t)tid * 4;
+    using K = Partials<LOSS ? kLossV : kMomentsV>;
     __shared__ double sm[kThreads / 64][kLossV];
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const double x = v == MXV_PPO_RATIO_MIN ? group_value<Min, V>(t, l0, v) : v == MXV_PPO_RATIO_MAX ? group_value<Max, V>(t, l0, v) : group_value<Add, V>(t, l0, v);
-        if (lane == 0) sm[wave][v] = x;
-    }
-    __syncthreads();
+    fold_level<K>(sm, t.in, t.count);
     if (!t.last) {
-        if (tid < V) {
-            const double total = tid == MXV_PPO_RATIO_MIN ? four_waves<Min>(sm, tid) : tid == MXV_PPO_RATIO_MAX ? four_waves<Max>(sm, tid) : four_waves<Add>(sm, tid);
-            t.out[(int64_t)blockIdx.x * V + tid] = total;
-        }
+        write_partials<K>(sm, t.out);
         return;
     }
-    if (tid != 0) return;
+    if (threadIdx.x != 0) return;
     const double Mf = (double)t.M;
     if constexpr (LOSS) {
         const double policy_loss = -(four_waves<Add>(sm, 0) / Mf);
@@ -282,18 +208,6 @@ __global__ void __launch_bounds__(kThreads) ppo_bwd(const PpoArgs p) {
 }
 
 // ---- host ----
-int64_t leaves_of(int64_t M) { return (M + kLeafRows - 1) / kLeafRows; }
-
-// doubles of workspace per value of a leaf: the leaves, and every level of the tree that is not the last
-int64_t workspace_slots(int64_t M) {
-    int64_t count = leaves_of(M), slots = count;
-    while (count > kTreeFan) {
-        count = (count + kTreeFan - 1) / kTreeFan;
-        slots += count;
-    }
-    return slots;
-}
-
 using PCall = Call<mxv::PpoCall>;
 
 int check_rows(const PCall &call, int64_t M) {
@@ -308,11 +222,7 @@ int check_finite(const PCall &call, const char *name, double v) {
 }
 
 int check_workspace(const PCall &call, int64_t M, const void *workspace, int64_t workspace_bytes) {
-    if (!workspace) return call.bad("%s: workspace pointer is NULL", call.api);
-    const int64_t need = mxv_ppo_workspace_bytes(M);
-    if (workspace_bytes < need)
-        return call.bad("%s: workspace_bytes = %lld is below mxv_ppo_workspace_bytes(%lld) = %lld", call.api, (long long)workspace_bytes, (long long)M, (long long)need);
-    return MXV_OK;
+    return mxv::sum_tree::check_workspace(call, "mxv_ppo_workspace_bytes", M, workspace, workspace_bytes, mxv_ppo_workspace_bytes(M));
 }
 
 // what the forward and the backward of the loss check alike; fills the inputs of `p`
@@ -331,21 +241,6 @@ int check_loss(const PCall &call, int64_t M, const float *lp, const float *old, 
     p.lo = 1.0 - clip; p.hi = 1.0 + clip; p.ecoef = ecoef; p.vcoef = vcoef;
     p.M = M; p.tiles = (M + kThreads - 1) / kThreads;
     return MXV_OK;
-}
-
-// the levels of the tree over `leaves` partials of V values at the start of `ws`
-template <bool LOSS>
-int run_tree(const PCall &call, TreeArgs t, double *ws, int64_t leaves, void *stream) {
-    constexpr int V = LOSS ? kLossV : kMomentsV;
-    int64_t count = leaves, offset = leaves * V;
-    const double *in = ws;
-    for (;;) {
-        const int64_t groups = (count + kTreeFan - 1) / kTreeFan;
-        t.in = in; t.count = count; t.last = groups == 1; t.out = t.last ? nullptr : ws + offset;
-        if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&ppo_tree<LOSS>), t, groups, stream)) return rc;
-        if (t.last) return MXV_OK;
-        in = t.out; offset += groups * V; count = groups;
-    }
 }
 
 }  // namespace
@@ -372,7 +267,7 @@ int mxv_ppo_advantage_moments(void *stream, int64_t M, const float *advantages_d
     if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&moments_leaf), a, leaves, stream)) return rc;
     TreeArgs t{};
     t.M = M; t.eps = eps; t.moments = moments_out_dev;
-    return run_tree<false>(call, t, a.partials, leaves, stream);
+    return run_tree(call, reinterpret_cast<const void *>(&ppo_tree<false>), kMomentsV, t, a.partials, leaves, stream);
 }
 
 int mxv_ppo_clip_loss(void *stream, int64_t M, const float *log_prob_dev, const float *old_log_prob_dev, const float *advantages_dev,
@@ -400,7 +295,7 @@ int mxv_ppo_clip_loss(void *stream, int64_t M, const float *log_prob_dev, const 
     TreeArgs t{};
     t.M = M; t.has_ent = entropy_dev != nullptr; t.has_val = values_dev != nullptr; t.ecoef = entropy_coef; t.vcoef = value_coef;
     t.loss = loss_out_dev; t.stats = stats_out_dev;
-    return run_tree<true>(call, t, p.partials, leaves, stream);
+    return run_tree(call, reinterpret_cast<const void *>(&ppo_tree<true>), kLossV, t, p.partials, leaves, stream);
 }
 
 int mxv_ppo_clip_loss_backward(void *stream, int64_t M, const float *log_prob_dev, const float *old_log_prob_dev, const float *advantages_dev,

@@ -18,8 +18,10 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native
+from ._policy_args import LEAF_ROWS       # rows per leaf of the sum tree, and leaves per group of a level
 from ._policy_args import _check as _raise
-from ._policy_args import _one_device, _ptr, _vector
+from ._policy_args import _one_device, _ptr, _tree_launches, _vector
+from ._policy_args import _workspace as _shared_workspace
 from .returns import _scalar
 
 PPO_EXPORTS = ("mxv_ppo_workspace_bytes", "mxv_ppo_advantage_moments", "mxv_ppo_clip_loss", "mxv_ppo_clip_loss_backward", "mxv_ppo_last_error")
@@ -27,7 +29,6 @@ PPO_EXPORTS = ("mxv_ppo_workspace_bytes", "mxv_ppo_advantage_moments", "mxv_ppo_
 POLICY_LOSS, VALUE_LOSS, ENTROPY, APPROX_KL, APPROX_KL3, CLIP_FRACTION, RATIO_MIN, RATIO_MAX = range(8)
 STATS = 8
 STAT_NAMES = ("policy_loss", "value_loss", "entropy", "approx_kl", "approx_kl3", "clip_fraction", "ratio_min", "ratio_max")
-LEAF_ROWS = 1024        # rows per leaf of the sum tree, and leaves per group of a level (kLeafRows, kTreeFan of gym_amd/csrc/mxv_ppo.hip)
 
 lib = _native.lib
 _P, _D, _I64 = C.c_void_p, C.c_double, C.c_int64
@@ -58,24 +59,11 @@ def workspace_bytes(rows: int) -> int:
 def launches(rows: int) -> int:
     """Kernel launches of one forward (and of advantage_moments) on `rows` rows: the leaves, then one per level of the tree."""
     workspace_bytes(rows)
-    count, n = -(-int(rows) // LEAF_ROWS), 2
-    while count > LEAF_ROWS:
-        count, n = -(-count // LEAF_ROWS), n + 1
-    return n
+    return _tree_launches(rows)
 
 
 def _workspace(t, workspace, M, dev):
-    """The caller's workspace (a contiguous 1-D uint8 or float64 tensor that is large enough), or a fresh one."""
-    need = workspace_bytes(M)
-    if workspace is None:
-        return t.empty(need // 8, dtype=t.float64, device=dev), need
-    w = _vector(t, workspace, "workspace", getattr(workspace, "shape", ()), (t.uint8, t.float64))
-    if w.dim() != 1 or tuple(workspace.shape) != tuple(w.shape):
-        raise ValueError(f"workspace must be 1-D, got shape {tuple(workspace.shape)}")
-    have = w.numel() * w.element_size()
-    if have < need:
-        raise ValueError(f"workspace holds {have} bytes, {M} rows need {need} (gym_amd.ppo.workspace_bytes)")
-    return w, have
+    return _shared_workspace(t, workspace, M, dev, workspace_bytes(M), "ppo")
 
 
 def _no_grad_input(t, x, name):

@@ -21,6 +21,32 @@ from test_policy_eval_resources import HIPCC, _resources
 CSRC = os.path.join(ROOT, "gym_amd", "csrc")
 SRC = os.path.join(CSRC, "mxv_c51.hip")
 COMBINE_LDS = 4 * 8 * 8
+TREE = os.path.join(CSRC, "mxv_sum_tree.hpp")
+# what only mxv_sum_tree.hpp defines: no file that includes it keeps a copy (tests/test_ppo_resources.py, test_dqn_resources.py and the
+# normalisation kernels' test in test_kernel_resources.py use the same list)
+TREE_COPIES = (r"\bwave_tree\s*\(double", r"\bwave_tree_sum\b", r"struct\s+(Add|Min|Max)\b", r"\bdpp_f64\s*\(double", r"\bgroup_value\s*\(const",
+               r"\bleaves_of\s*\(int64_t", r"\bint\s+run_tree\s*\(const", r"\bkLeafRows\s*=", r"\bkTreeFan\s*=", r"permlane\d+_swap")
+TREE_BARRIER_HELPERS = ("leave_wave_values(", "fold_level<")      # each ends in the one barrier of the kernel that calls it
+
+
+def tree_header():
+    """mxv_sum_tree.hpp without its comments: no read-modify-write memory operation, no assembly, no shuffle, and one barrier in each of the
+    two helpers that leave the waves' values in LDS."""
+    tree = re.sub(r"//.*", "", open(TREE).read())
+    for word in ("atomic", "asm", "__shfl", "#if MXV_"):
+        assert word not in tree, word
+    assert tree.count("__syncthreads()") == len(TREE_BARRIER_HELPERS) and "__shared__" not in tree
+    for helper in ("void leave_wave_values(", "void fold_level("):
+        body = tree[tree.index(helper):]
+        assert body[:body.index("\n}\n")].rstrip().endswith("__syncthreads();"), helper
+    return tree
+
+
+def barriers(src):
+    """Barriers of a kernel source: its own, and one for every call of a helper of mxv_sum_tree.hpp that ends in one."""
+    return src.count("__syncthreads()") + sum(src.count(h) for h in TREE_BARRIER_HELPERS)
+
+
 # symbol: (waves per SIMD, VGPR bound, LDS bytes) as reported at the time of the change; reported VGPRs in the comments
 BUDGET = {
     "_ZN12_GLOBAL__N_18c51_rowsENS_7C51ArgsE": (8, 40, 0),               # 38
@@ -71,18 +97,16 @@ def test_the_source_shares_the_rule_the_tree_and_the_host_checks():
     assert "kThreads" in src and "kMaxActions" in src
     assert "Call<mxv::C51Call>" in src and "check_ranges(" in src and "check_stride(" in src
     for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b",
-                 r"\bwave_tree\s*\(double", r"struct\s+(Add|Min|Max)\b", r"\bdouble\s+(exp_rule|log_rule|e_of)\b", r"\b(exp|log|expf|logf|__expf|__logf)\s*\("):
+                 r"\bdouble\s+(exp_rule|log_rule|e_of)\b", r"\b(exp|log|expf|logf|__expf|__logf)\s*\(") + TREE_COPIES:
         assert not re.search(copy, src), copy
     assert not RULE_NAMES.search(src)      # none of the rule's constants is defined here
     assert "e_of(" in src and "log_rule(" in src
     # the only atomics would be on integer types: there is none at all, no assembly and no shuffle
     for word in ("atomic", "asm", "__shfl", "#if MXV_"):
         assert word not in src, word
-    tree = re.sub(r"//.*", "", open(os.path.join(CSRC, "mxv_sum_tree.hpp")).read())
-    for word in ("atomic", "asm", "__shfl", "#if MXV_"):
-        assert word not in tree, word
+    tree_header()
     # one combine in each of the two kernels that reduce over rows
-    assert src.count("__shared__") == 2 and src.count("__syncthreads()") == 2
+    assert src.count("__shared__") == 2 and barriers(src) == 2
     for script in ("build.sh", "build_asan.sh"):
         assert "mxv_c51.hip" in open(os.path.join(CSRC, script)).read(), script
     flags = open(os.path.join(CSRC, "build.sh")).read()
@@ -92,11 +116,13 @@ def test_the_source_shares_the_rule_the_tree_and_the_host_checks():
 
 
 def test_the_launch_constants_the_module_exports_are_the_kernels():
-    from gym_amd import c51
+    from gym_amd import c51, dqn, ppo
 
     src = open(SRC).read()
     rule = open(os.path.join(CSRC, "mxv_policy_rule.hpp")).read()
-    assert f"constexpr int kLeafRows = {c51.LEAF_ROWS};" in src and f"constexpr int kTreeFan = {c51.LEAF_ROWS};" in src
+    tree = open(TREE).read()
+    assert f"constexpr int kLeafRows = {c51.LEAF_ROWS};" in tree and f"constexpr int kTreeFan = {c51.LEAF_ROWS};" in tree
+    assert ppo.LEAF_ROWS == dqn.LEAF_ROWS == c51.LEAF_ROWS      # the one tree of the three losses
     assert f"constexpr int kGridX = 1 << {c51.GRID_X.bit_length() - 1};" in src and c51.GRID_X & (c51.GRID_X - 1) == 0
     assert "constexpr int kWaves = kThreads / 64;" in src and f"constexpr int kThreads = {64 * c51.TILE_ROWS};" in rule
     assert f"constexpr int kMaxBlocks = {c51.MAX_BLOCKS};" in rule and f"constexpr int kMaxAtoms = {c51.MAX_ATOMS};" in src

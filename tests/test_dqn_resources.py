@@ -5,8 +5,8 @@ everything in registers: no scratch, no spilled vector or scalar register, no AG
 registers (rounded up to the allocation granule of 8) the compiler reported when the kernels were written (DESIGN.md §17 records the
 figures).  The only LDS is the four-wave combine — 4 waves x 8 values x 8 bytes in the kernels that reduce — and the backward's staging
 of the loop instantiation: one float and one column index per row of a tile, 256 x 8 bytes; the straight-line backward has none.  Read
-from the compiler's resource report of the code object only.  Also: the source includes the shared rule and host checks and defines no
-copy of them, and has no read-modify-write memory operation, no assembly and no shuffle."""
+from the compiler's resource report of the code object only.  Also: the source includes the shared rule, the shared sum tree and the host
+checks and defines no copy of them, and neither it nor the tree has a read-modify-write memory operation, assembly or a shuffle."""
 import os
 import re
 import shutil
@@ -16,6 +16,7 @@ import tempfile
 import pytest
 
 from conftest import ROOT
+from test_c51_resources import TREE_COPIES, barriers, tree_header
 from test_policy_eval_resources import HIPCC, _resources
 
 SRC = os.path.join(ROOT, "gym_amd", "csrc", "mxv_dqn.hip")
@@ -67,13 +68,15 @@ def test_every_kernel_stays_in_registers_and_the_lds_is_the_combine_and_the_stag
 def test_the_source_shares_the_rule_and_the_host_checks():
     src = re.sub(r"//.*", "", open(SRC).read())
     assert '#include "mxv_policy_rule.hpp"' in src and '#include "mxv_policy_host.hpp"' in src and "kThreads" in src and "kMaxActions" in src
+    assert '#include "mxv_sum_tree.hpp"' in src and "wave_tree<" in src and "run_tree(" in src
     assert "Call<mxv::DqnCall>" in src and "check_ranges(" in src and "check_stride(" in src
-    for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b"):
+    for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b") + TREE_COPIES:
         assert not re.search(copy, src), copy
     for word in ("atomic", "asm", "__shfl"):
         assert word not in src, word
+    tree_header()      # nor has the shared tree any of them
     # one combine in each of the two kernels that reduce, and the two staging arrays of the loop backward between its two barriers
-    assert src.count("__shared__") == 4 and src.count("__syncthreads()") == 4
+    assert src.count("__shared__") == 4 and barriers(src) == 4
     for script in ("build.sh", "build_asan.sh"):
         assert "mxv_dqn.hip" in open(os.path.join(ROOT, "gym_amd", "csrc", script)).read(), script
     flags = open(os.path.join(ROOT, "gym_amd", "csrc", "build.sh")).read()

@@ -226,7 +226,14 @@ def test_tabular_trajectory_kernel_stays_lean():
 
 def test_normalisation_kernels_keep_their_pipelines():
     """mxv_norm.hip: the vector path of returns_sums_kernel waits for its ring with vmcnt(>= 9) — a derived value in the ring, or an exit
-    between the unrolled steps, shows up here as vmcnt(0..4) (round 4) — and reduces through DPP / permlane, not ds_bpermute."""
+    between the unrolled steps, shows up here as vmcnt(0..4) (round 4) — and reduces through DPP / permlane, not ds_bpermute: the butterfly
+    of mxv_sum_tree.hpp, of which the file keeps no copy."""
+    from test_c51_resources import TREE_COPIES
+
+    src = re.sub(r"//.*", "", open(os.path.join(ROOT, "gym_amd", "csrc", "mxv_norm.hip")).read())
+    assert '#include "mxv_sum_tree.hpp"' in src and "wave_tree<Add>(" in src
+    for copy in TREE_COPIES:
+        assert not re.search(copy, src), copy
     remarks, asm = _compile("mxv_norm.hip")
     for sym, floor in (("_ZN12_GLOBAL__N_119returns_sums_kernelIdEEvPKT_PKhS5_PdlidlS6_i", 12), ("_ZN12_GLOBAL__N_119returns_sums_kernelIfEEvPKT_PKhS5_PdlidlS6_i", 9)):
         body = _function_body(asm, sym)

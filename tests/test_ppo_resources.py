@@ -4,7 +4,8 @@ Every kernel — ppo_leaf, moments_leaf, the two instantiations of ppo_tree, ppo
 vector or scalar register, no AGPRs, and at least the occupancy and at most the vector registers (rounded up to the allocation granule
 of 8) the compiler reported when the kernels were written (DESIGN.md §15 records the figures).  The only LDS is the four-wave combine:
 4 waves x 8 values x 8 bytes in the kernels that reduce, none in the backward.  Read from the compiler's resource report of the code
-object only.  Also: the source includes the shared rule and defines no copy of it, and uses no atomics and no assembly."""
+object only.  Also: the source includes the shared rule and the shared sum tree and defines no copy of them, and neither it nor the tree
+uses atomics or assembly."""
 import os
 import re
 import shutil
@@ -14,6 +15,7 @@ import tempfile
 import pytest
 
 from conftest import ROOT
+from test_c51_resources import TREE_COPIES, barriers, tree_header
 from test_policy_eval_resources import HIPCC, _resources
 
 SRC = os.path.join(ROOT, "gym_amd", "csrc", "mxv_ppo.hip")
@@ -57,11 +59,13 @@ def test_every_kernel_stays_in_registers_and_the_only_lds_is_the_combine(remarks
 def test_the_source_shares_the_rule_and_uses_no_atomics_or_assembly():
     src = re.sub(r"//.*", "", open(SRC).read())
     assert '#include "mxv_policy_rule.hpp"' in src and "exp_rule(" in src and "kThreads" in src
-    for copy in (r"\bexp_rule\s*\(\s*double", r"\bkThreads\s*=", r"\bkExpC\b", r"\bkInvLn2\b", r"\bkMaxElems\s*="):
+    assert '#include "mxv_sum_tree.hpp"' in src and "wave_tree<" in src and "run_tree(" in src
+    for copy in (r"\bexp_rule\s*\(\s*double", r"\bkThreads\s*=", r"\bkExpC\b", r"\bkInvLn2\b", r"\bkMaxElems\s*=") + TREE_COPIES:
         assert not re.search(copy, src), copy
     for word in ("atomic", "asm", "__shfl"):
         assert word not in src, word
-    assert src.count("__shared__") == 3 and src.count("__syncthreads()") == 3      # one combine in each kernel that reduces
+    tree_header()      # nor has the shared tree any of them
+    assert src.count("__shared__") == 3 and barriers(src) == 3      # one combine in each kernel that reduces
     for script in ("build.sh", "build_asan.sh"):
         assert "mxv_ppo.hip" in open(os.path.join(ROOT, "gym_amd", "csrc", script)).read(), script
     flags = open(os.path.join(ROOT, "gym_amd", "csrc", "build.sh")).read()
