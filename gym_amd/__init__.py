@@ -45,6 +45,8 @@ _LAZY = {
     "categorical_q_values": ("gym_amd.c51", "categorical_q_values"),
     "rsample_squashed_gaussian": ("gym_amd.squashed", "rsample_squashed_gaussian"),
     "SquashedGaussianSampler": ("gym_amd.squashed", "SquashedGaussianSampler"),
+    "NStepReplayBuffer": ("gym_amd.nstep", "NStepReplayBuffer"),
+    "NStepPrioritizedReplayBuffer": ("gym_amd.nstep", "NStepPrioritizedReplayBuffer"),
 }
 
 def __getattr__(name):

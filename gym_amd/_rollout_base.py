@@ -156,6 +156,21 @@ class _RolloutBase:
         return PrioritizedReplayBuffer(capacity, shape, obs_dtype=dtype, action_dtype=self._policy_head[1],
                                        seed=self.handle._action_seed if seed is None else seed, device=self.device, alpha=alpha, eps=eps)
 
+    def nstep_replay_buffer(self, capacity, n_step, gamma, prioritized=False, alpha=0.6, eps=1e-6, seed=None):
+        """A gym_amd.nstep.NStepReplayBuffer — or, with prioritized=True, an NStepPrioritizedReplayBuffer with `alpha` and `eps` — for this
+        rollout's transitions: replay_buffer() whose rows are n-step returns with a per-row discount."""
+        from .nstep import NStepPrioritizedReplayBuffer, NStepReplayBuffer
+
+        layout = getattr(self, "_replay_obs", None)
+        if layout is None:
+            raise ValueError(f"{type(self).__name__}: nstep_replay_buffer() needs trajectories of [K, N, ...] observation rows; build a "
+                             "gym_amd.NStepReplayBuffer with the shape and dtype of the rows you record")
+        shape, dtype = layout
+        kw = dict(obs_dtype=dtype, action_dtype=self._policy_head[1], seed=self.handle._action_seed if seed is None else seed, device=self.device)
+        if prioritized:
+            return NStepPrioritizedReplayBuffer(capacity, shape, n_step, gamma, alpha=alpha, eps=eps, **kw)
+        return NStepReplayBuffer(capacity, shape, n_step, gamma, **kw)
+
     def synchronize(self):
         """Wait for the engine's stream; raises if a step saw an out-of-range action."""
         try:

@@ -40,6 +40,9 @@ struct PrioCall {   // include/mxv_prio.h: mxv_prio_last_error
 struct C51Call {   // include/mxv_c51.h: mxv_c51_last_error
     std::string error;
 };
+struct NStepCall {   // include/mxv_nstep.h: mxv_nstep_last_error
+    std::string error;
+};
 
 namespace policy_host {
 

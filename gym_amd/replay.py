@@ -186,13 +186,18 @@ class ReplayBuffer:
         dev = _one_device((("the buffer", self._obs), ("first_obs" if K is not None else "obs", first2), ("obs" if K is not None else "next_obs", obs2),
                            ("final_obs", fin2), ("actions", act), ("reward", rew), ("terminated", term), ("truncated", trunc)))
         with t.cuda.device(dev):
-            _check(lib.mxv_replay_insert(t.cuda.current_stream(dev).cuda_stream, self.capacity, self.W, 1 if K is None else K, N,
-                                         first2.data_ptr(), first_ld, obs2.data_ptr(), obs_ld, _ptr(fin2), fin_ld, act.data_ptr(), self._action_bytes,
-                                         rew.data_ptr(), rew.element_size(), term.data_ptr(), _ptr(trunc), self._count, _ptr(self._state),
-                                         self._obs.data_ptr(), self._next.data_ptr(), self._action.data_ptr(), self._reward.data_ptr(),
-                                         self._term.data_ptr()))
+            self._store(t.cuda.current_stream(dev).cuda_stream, 1 if K is None else K, N, first2.data_ptr(), first_ld, obs2.data_ptr(), obs_ld,
+                        _ptr(fin2), fin_ld, act.data_ptr(), rew.data_ptr(), rew.element_size(), term.data_ptr(), _ptr(trunc))
         if self._state is None:
             self._count += R
+
+    def _store(self, stream, K, N, first, first_ld, obs, obs_ld, final, final_ld, actions, reward, reward_bytes, terminated, truncated):
+        """The library call of an insert, on the prepared arguments of _insert (device addresses, row strides in dwords): what a
+        subclass with another insert rule overrides."""
+        _check(lib.mxv_replay_insert(stream, self.capacity, self.W, K, N, first, first_ld, obs, obs_ld, final, final_ld, actions,
+                                     self._action_bytes, reward, reward_bytes, terminated, truncated, self._count, _ptr(self._state),
+                                     self._obs.data_ptr(), self._next.data_ptr(), self._action.data_ptr(), self._reward.data_ptr(),
+                                     self._term.data_ptr()))
 
     def add_chunk(self, first_obs, traj):
         """Stores the K * N transitions of a [K, N] chunk in ONE launch (two after enable_graph_capture()).
