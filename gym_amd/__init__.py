@@ -47,6 +47,8 @@ _LAZY = {
     "SquashedGaussianSampler": ("gym_amd.squashed", "SquashedGaussianSampler"),
     "NStepReplayBuffer": ("gym_amd.nstep", "NStepReplayBuffer"),
     "NStepPrioritizedReplayBuffer": ("gym_amd.nstep", "NStepPrioritizedReplayBuffer"),
+    "quantile_dqn_loss": ("gym_amd.qr", "quantile_dqn_loss"),
+    "quantile_q_values": ("gym_amd.qr", "quantile_q_values"),
 }
 
 def __getattr__(name):

@@ -43,6 +43,9 @@ struct C51Call {   // include/mxv_c51.h: mxv_c51_last_error
 struct NStepCall {   // include/mxv_nstep.h: mxv_nstep_last_error
     std::string error;
 };
+struct QrCall {   // include/mxv_qr.h: mxv_qr_last_error
+    std::string error;
+};
 
 namespace policy_host {
 

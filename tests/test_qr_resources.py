@@ -1,0 +1,104 @@
+"""Resource budget of gym_amd/csrc/mxv_qr.hip, guarded on the CPU (hipcc cross-compiles gfx950 without a GPU; seconds).
+
+Every kernel — qr_rows, qr_leaf, qr_tree, qr_bwd, qr_q — keeps everything in registers: no scratch, no spilled vector or scalar
+register, no AGPRs, and at least the occupancy and at most the vector registers (rounded up to the allocation granule of 8) the compiler
+reported when the kernels were written (DESIGN.md §23 records the figures).  The only LDS is the four-wave combine — 4 waves x 8 values
+x 8 bytes — in the two kernels that reduce over rows; the kernels that own a row per wave have none.  Read from the compiler's
+resource report of the code object only.  Also: the source includes the shared rule, the shared sum tree and the host checks and
+defines no copy of them, and has no read-modify-write memory operation, no assembly and no shuffle."""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+from conftest import ROOT
+from policy_host import RULE_NAMES
+from test_c51_resources import COMBINE_LDS, TREE, TREE_COPIES, barriers, tree_header
+from test_policy_eval_resources import HIPCC, _resources
+
+CSRC = os.path.join(ROOT, "gym_amd", "csrc")
+SRC = os.path.join(CSRC, "mxv_qr.hip")
+KERNELS = ("qr_rows", "qr_leaf", "qr_tree", "qr_bwd", "qr_q")
+
+# symbol: (waves per SIMD, VGPR bound, LDS bytes) as reported at the time of the change; reported VGPRs in the comments
+BUDGET = {
+    "_ZN12_GLOBAL__N_17qr_rowsENS_6QrArgsE": (8, 40, 0),                # 34
+    "_ZN12_GLOBAL__N_17qr_leafENS_8LeafArgsE": (8, 48, COMBINE_LDS),    # 45
+    "_ZN12_GLOBAL__N_17qr_treeENS_8TreeArgsE": (8, 48, COMBINE_LDS),    # 45
+    "_ZN12_GLOBAL__N_16qr_bwdENS_6QrArgsE": (8, 32, 0),                 # 28
+    "_ZN12_GLOBAL__N_14qr_qENS_6QrArgsE": (8, 24, 0),                   # 18
+}
+
+
+@pytest.fixture(scope="module")
+def remarks():
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    d = tempfile.mkdtemp(prefix="mxv_qr_res_")
+    try:
+        p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-c", SRC,
+                            "-o", os.path.join(d, "k.o"), "-Rpass-analysis=kernel-resource-usage"], cwd=d, capture_output=True, text=True,
+                           timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        yield p.stderr
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def test_every_kernel_stays_in_registers_and_the_only_lds_is_the_combine(remarks):
+    res = _resources(remarks)
+    assert sorted(res) == sorted(BUDGET)
+    for kernel, (occupancy, vgprs, lds) in BUDGET.items():
+        r = res[kernel]
+        print(kernel, r)
+        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["AGPRs"] == 0, (kernel, r)
+        assert r["LDS Size"] == lds, (kernel, r)
+        assert r["Occupancy"] >= occupancy and r["VGPRs"] <= vgprs, (kernel, r)
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("## 23."):]
+    for name in KERNELS:      # the table of §23: | kernel | VGPRs | SGPRs | waves/SIMD | LDS | scratch |
+        row = re.search(rf"\| `{name}` \| (\d+) \| \d+ \| (\d+) \| (\d+) \| 0 \|", section)
+        assert row, name
+        r = next(v for k, v in res.items() if f"{name}E" in k)
+        assert (r["VGPRs"], r["Occupancy"], r["LDS Size"]) == tuple(int(x) for x in row.groups()), (name, r, row.groups())
+
+
+def test_the_source_shares_the_rule_the_tree_and_the_host_checks():
+    src = re.sub(r"//.*", "", open(SRC).read())
+    for header in ("mxv_policy_rule.hpp", "mxv_policy_host.hpp", "mxv_sum_tree.hpp"):
+        assert f'#include "{header}"' in src, header
+    assert "kThreads" in src and "kMaxActions" in src and "kMaxBlocks" not in src      # qr_q strides through Call::launch's grid_of
+    assert "Call<mxv::QrCall>" in src and "check_ranges(" in src and "check_stride(" in src and "check_workspace(" in src
+    for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b",
+                 r"\bint\s+check_workspace\b", r"\bdouble\s+(exp_rule|log_rule|e_of)\b", r"\b(exp|log|expf|logf|__expf|__logf)\s*\(") + TREE_COPIES:
+        assert not re.search(copy, src), copy
+    assert not RULE_NAMES.search(src)      # none of the rule's constants is defined here
+    assert "wave_tree<Add>(" in src and "lane_value(" in src and "run_tree(" in src and "fold_level<Partials>(" in src
+    for word in ("atomic", "asm", "__shfl", "#if MXV_"):
+        assert word not in src, word
+    tree_header()
+    # one combine in each of the two kernels that reduce over rows
+    assert src.count("__shared__") == 2 and barriers(src) == 2
+    assert sorted(re.findall(r"__global__ void __launch_bounds__\(kThreads\) (\w+)\(", src)) == sorted(KERNELS)
+    for script in ("build.sh", "build_asan.sh"):
+        assert "mxv_qr.hip" in open(os.path.join(CSRC, script)).read(), script
+    flags = open(os.path.join(CSRC, "build.sh")).read()
+    assert "-ffp-contract=off" in flags and "-fno-fast-math" in flags and "-ffast-math" not in flags
+    host = open(os.path.join(CSRC, "mxv_policy_host.hpp")).read()
+    assert "struct QrCall {" in host and "struct C51Call {" in host
+
+
+def test_the_launch_constants_the_module_exports_are_the_kernels():
+    from gym_amd import c51, qr
+
+    src = open(SRC).read()
+    rule = open(os.path.join(CSRC, "mxv_policy_rule.hpp")).read()
+    tree = open(TREE).read()
+    assert f"constexpr int kLeafRows = {qr.LEAF_ROWS};" in tree and f"constexpr int kTreeFan = {qr.LEAF_ROWS};" in tree
+    assert c51.LEAF_ROWS == qr.LEAF_ROWS and (c51.TILE_ROWS, c51.GRID_X, c51.MAX_BLOCKS) == (qr.TILE_ROWS, qr.GRID_X, qr.MAX_BLOCKS)
+    assert f"constexpr int kGridX = 1 << {qr.GRID_X.bit_length() - 1};" in src and qr.GRID_X & (qr.GRID_X - 1) == 0
+    assert "constexpr int kWaves = kThreads / 64;" in src and f"constexpr int kThreads = {64 * qr.TILE_ROWS};" in rule
+    assert f"constexpr int kMaxBlocks = {qr.MAX_BLOCKS};" in rule and f"constexpr int kMaxQuantiles = {qr.MAX_QUANTILES};" in src
