@@ -30,19 +30,21 @@
 #include "mxv_policy_host.hpp"
 #include "mxv_policy_rule.hpp"
 #include "mxv_sum_tree.hpp"
+#include "mxv_value_loss.hpp"
 
 namespace {
 
 using namespace mxv::rule;
 using namespace mxv::policy_host;
 using namespace mxv::sum_tree;
+using namespace mxv::value_loss;
 
-constexpr int kWaves = kThreads / 64;    // rows per tile of c51_rows, c51_bwd and c51_q: one per wave
-constexpr int kV = MXV_C51_STATS;        // partials of a leaf: sums of term, qa, y, ent, cm; max ce, min qa, max qa
-constexpr int kCols = 6;                 // columns a row leaves in the workspace: term, qa, y, ent, cm, ce
 constexpr int kMaxAtoms = 64;
-constexpr int kGridX = 1 << 16;          // c51_rows, c51_bwd: tiles along x of the grid; beyond, y counts slices of kGridX tiles, and z
-constexpr int kGridY = 1 << 15;          // slices of kGridY of those (2^38 tiles of 2^40 rows fit)
+// the slots of mxv_value_loss.hpp's partials and finish: sums of term, qa, y, ent, cm; max ce, min qa, max qa; a row's columns are term,
+// qa, y, ent, cm, ce
+static_assert(MXV_C51_STATS == kV && MXV_C51_LOSS_TERM == 0 && MXV_C51_Q_TAKEN_MEAN == 1 && MXV_C51_TARGET_MEAN == 2 && MXV_C51_ENTROPY_MEAN == 3 &&
+                  MXV_C51_CLIPPED_MASS_MEAN == 4 && MXV_C51_ROW_LOSS_MAX == 5 && MXV_C51_Q_TAKEN_MIN == 6 && MXV_C51_Q_TAKEN_MAX == 7,
+              "mxv_c51.h's stats are the slots of mxv_value_loss.hpp");
 
 struct C51Args {
     const float *logits, *target_probs, *reward, *next, *online, *weights;
@@ -56,22 +58,6 @@ struct C51Args {
     double gamma, v_min, v_max, dz, z_top;      // dz = (v_max - v_min) / (Z - 1); z_top = (double)(Z - 1)
     int64_t M, ld, next_ld, online_ld, tiles;
     int32_t A, Z, i64;
-};
-
-struct LeafArgs {
-    const double *cols;              // [6][M]
-    double *partials;                // [leaves][8]
-    int64_t M;
-    int32_t last;                    // one leaf: finish here
-    float *loss, *stats;
-};
-
-struct TreeArgs {
-    const double *in;                // [count][8]
-    double *out;                     // [groups][8]; unused by the last level
-    int64_t count, M;
-    int32_t last;
-    float *loss, *stats;
 };
 
 __device__ __forceinline__ bool any_lane(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0; }
@@ -171,10 +157,6 @@ __device__ __forceinline__ Row row_of(const C51Args &p, int64_t i, int k) {
     return w;
 }
 
-__device__ __forceinline__ int wave_of_block() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-// the tile of a workgroup of c51_rows and c51_bwd (grid_rows below)
-__device__ __forceinline__ int64_t tile_of_block() { return ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * kGridX + blockIdx.x; }
-
 // ---- forward: the rows ----
 __global__ void __launch_bounds__(kThreads) c51_rows(const C51Args p) {
     const int wave = wave_of_block(), lane = threadIdx.x & 63;
@@ -198,69 +180,15 @@ __global__ void __launch_bounds__(kThreads) c51_rows(const C51Args p) {
     }
 }
 
-// ---- forward: the leaves and the tree ----
-// which of a leaf's partials is a minimum, which a maximum; the others are sums
-struct Partials {
-    static constexpr int V = kV;
-    static constexpr bool is_min(int v) { return v == MXV_C51_Q_TAKEN_MIN; }
-    static constexpr bool is_max(int v) { return v == MXV_C51_ROW_LOSS_MAX || v == MXV_C51_Q_TAKEN_MAX; }
-};
-
-// the first lane writes the loss and the diagnostics from the last group's four waves
-__device__ __forceinline__ void finish(const double (*sm)[kV], int64_t M, float *loss_out, float *stats) {
-    const double Mf = (double)M;
-    const double loss = four_waves<Add>(sm, MXV_C51_LOSS_TERM) / Mf;
-    loss_out[0] = to_f32(loss);
-    stats[MXV_C51_LOSS_TERM] = to_f32(loss);
-    stats[MXV_C51_Q_TAKEN_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_Q_TAKEN_MEAN) / Mf);
-    stats[MXV_C51_TARGET_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_TARGET_MEAN) / Mf);
-    stats[MXV_C51_ENTROPY_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_ENTROPY_MEAN) / Mf);
-    stats[MXV_C51_CLIPPED_MASS_MEAN] = to_f32(four_waves<Add>(sm, MXV_C51_CLIPPED_MASS_MEAN) / Mf);
-    stats[MXV_C51_ROW_LOSS_MAX] = to_f32(four_waves<Max>(sm, MXV_C51_ROW_LOSS_MAX) + 0.0);      // + 0.0: a zero of either sign leaves as +0.0
-    stats[MXV_C51_Q_TAKEN_MIN] = to_f32(four_waves<Min>(sm, MXV_C51_Q_TAKEN_MIN) + 0.0);
-    stats[MXV_C51_Q_TAKEN_MAX] = to_f32(four_waves<Max>(sm, MXV_C51_Q_TAKEN_MAX) + 0.0);
-}
-
+// ---- forward: the leaves and the tree (mxv_value_loss.hpp) ----
 __global__ void __launch_bounds__(kThreads) c51_leaf(const LeafArgs a) {
-    const int tid = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
-    double s = 0.0, sq = 0.0, sy = 0.0, se = 0.0, sc = 0.0, mx_ce = Max::identity(), mn_q = Min::identity(), mx_q = Max::identity();
-#pragma unroll
-    for (int j = 0; j < kLeafRows / kThreads; ++j) {
-        const int64_t i = row0 + j * kThreads + tid;
-        if (i >= a.M) continue;
-        const double *c = a.cols + i;
-        const double qa = c[a.M], ce = c[5 * a.M];
-        s = s + c[0];
-        sq = sq + qa;
-        sy = sy + c[2 * a.M];
-        se = se + c[3 * a.M];
-        sc = sc + c[4 * a.M];
-        mx_ce = ce > mx_ce ? ce : mx_ce;      // a NaN compares false: skipped
-        mn_q = qa < mn_q ? qa : mn_q;
-        mx_q = qa > mx_q ? qa : mx_q;
-    }
     __shared__ double sm[kThreads / 64][kV];
-    // a batch of one leaf: the one tree level it would pass through adds +0.0 to every sum and nothing else
-    const double zero = a.last ? 0.0 : -0.0;
-    const double t[kV] = {wave_tree<Add>(s) + zero,  wave_tree<Add>(sq) + zero, wave_tree<Add>(sy) + zero, wave_tree<Add>(se) + zero,
-                          wave_tree<Add>(sc) + zero, wave_tree<Max>(mx_ce),     wave_tree<Min>(mn_q),      wave_tree<Max>(mx_q)};
-    leave_wave_values(sm, t);
-    if (!a.last) {
-        write_partials<Partials>(sm, a.partials);
-        return;
-    }
-    if (tid == 0) finish(sm, a.M, a.loss, a.stats);
+    leaf_columns(sm, a);
 }
 
 __global__ void __launch_bounds__(kThreads) c51_tree(const TreeArgs t) {
     __shared__ double sm[kThreads / 64][kV];
-    fold_level<Partials>(sm, t.in, t.count);
-    if (!t.last) {
-        write_partials<Partials>(sm, t.out);
-        return;
-    }
-    if (threadIdx.x == 0) finish(sm, t.M, t.loss, t.stats);
+    tree_level(sm, t);
 }
 
 // ---- backward ----
@@ -298,9 +226,6 @@ __global__ void __launch_bounds__(kThreads) c51_q(const C51Args p) {
 }
 
 // ---- host ----
-// doubles of workspace: the six columns of the rows, the leaves' partials, and every level of the tree that is not the last
-int64_t workspace_doubles(int64_t M) { return kCols * M + workspace_slots(M) * kV; }
-
 using CCall = Call<mxv::C51Call>;
 
 int check_support(const CCall &call, int32_t Z, double v_min, double v_max) {
@@ -321,33 +246,18 @@ void fill_support(C51Args &p, int32_t A, int32_t Z, double v_min, double v_max) 
     p.dz = (v_max - v_min) / p.z_top;
 }
 
+constexpr ArgNames kNames = {"logits", "target_probs", "next_logits", "next_logits_online"};
+
 // what the forward and the backward check alike; fills the inputs of `p`
 int check_loss(const CCall &call, int64_t M, int32_t A, int32_t Z, const float *logits, int64_t ld, const void *actions, int32_t action_bytes,
                const float *target_probs, const float *reward, const uint8_t *terminated, const float *next, int64_t next_ld, const float *online,
                int64_t online_ld, double gamma, double v_min, double v_max, const float *weights, C51Args &p) {
-    if (!logits) return call.bad("%s: logits pointer is NULL", call.api);
-    if (!actions) return call.bad("%s: actions pointer is NULL", call.api);
-    if (M < 1) return call.bad("%s: M = %lld must be at least 1", call.api, (long long)M);
-    if (M > kMaxElems) return call.bad("%s: M = %lld is beyond 2^40 rows", call.api, (long long)M);
-    if (A < 1 || A > kMaxActions) return call.bad("%s: A = %d must be in 1..%d", call.api, (int)A, kMaxActions);
+    if (int rc = check_batch(call, kNames, logits, actions, M, A)) return rc;
     if (int rc = check_support(call, Z, v_min, v_max)) return rc;
-    if (int rc = check_rows_ld(call, "logits_ld", ld, M, A, Z)) return rc;
-    if (action_bytes != 4 && action_bytes != 8) return call.bad("%s: action_bytes = %d must be 4 (int32) or 8 (int64)", call.api, (int)action_bytes);
-    const bool any_boot = reward || terminated || next;
-    if (target_probs && any_boot)
-        return call.bad("%s: target_probs is given together with reward, terminated or next_logits: exactly one target mode", call.api);
-    if (target_probs && online) return call.bad("%s: next_logits_online is given with target_probs: it belongs to the bootstrap mode", call.api);
-    if (!target_probs && !any_boot)
-        return call.bad("%s: neither target_probs nor reward, terminated and next_logits are given: exactly one target mode", call.api);
-    if (!target_probs) {
-        if (!reward) return call.bad("%s: reward pointer is NULL in the bootstrap mode", call.api);
-        if (!terminated) return call.bad("%s: terminated pointer is NULL in the bootstrap mode", call.api);
-        if (!next) return call.bad("%s: next_logits pointer is NULL in the bootstrap mode", call.api);
-        if (int rc = check_rows_ld(call, "next_logits_ld", next_ld, M, A, Z)) return rc;
-        if (online)
-            if (int rc = check_rows_ld(call, "next_logits_online_ld", online_ld, M, A, Z)) return rc;
-    }
-    if (!std::isfinite(gamma)) return call.bad("%s: gamma = %g must be finite", call.api, gamma);
+    const auto check_ld = [&](const char *name, int64_t stride) { return check_rows_ld(call, name, stride, M, A, Z); };
+    if (int rc = check_ld("logits_ld", ld)) return rc;
+    if (int rc = check_targets(call, kNames, action_bytes, target_probs, reward, terminated, next, next_ld, online, online_ld, nullptr, gamma, check_ld))
+        return rc;
     p.logits = logits; p.actions = actions; p.target_probs = target_probs; p.reward = reward; p.terminated = terminated; p.next = next;
     p.online = online; p.weights = weights; p.gamma = gamma;
     p.M = M; p.ld = ld; p.next_ld = next_ld; p.online_ld = online_ld; p.tiles = (M + kWaves - 1) / kWaves;
@@ -370,19 +280,6 @@ void input_ranges(const C51Args &p, const float *g, Range *r) {
     r[6] = {"next_logits_online", (uintptr_t)p.online, p.online ? rows_bytes(p.M, p.online_ld, W) : 0, 4};
     r[7] = {"weights", (uintptr_t)p.weights, mb, 4};
     r[8] = {"grad_loss", (uintptr_t)g, 4, 4};
-}
-
-// One tile per workgroup, not workgroups striding over tiles: inside a tile loop the compiler keeps the 32 float64 constants of EXP and
-// LOG in scalar registers across the whole loop beside the kernel's arguments, and 10 to 16 of those spill.
-dim3 grid_rows(int64_t tiles) {
-    const int64_t slices = (tiles + kGridX - 1) / kGridX;
-    return dim3((unsigned)(tiles < kGridX ? tiles : kGridX), (unsigned)(slices < kGridY ? slices : kGridY), (unsigned)((slices + kGridY - 1) / kGridY));
-}
-
-int launch_rows(const CCall &call, const void *kernel, C51Args &a, void *stream) {
-    void *args[] = {&a};
-    const hipError_t e = hipLaunchKernel(kernel, grid_rows(a.tiles), dim3(kThreads), args, 0, (hipStream_t)stream);
-    return e == hipSuccess ? MXV_OK : call.hip_failed("kernel launch", e);
 }
 
 }  // namespace
@@ -413,18 +310,12 @@ int mxv_c51_loss(void *stream, int64_t M, int32_t A, int32_t Z, const float *log
                           {"loss_out", (uintptr_t)loss_out_dev, 4, 4},
                           {"stats_out", (uintptr_t)stats_out_dev, MXV_C51_STATS * 4, 4}};
     if (int rc = call.check_ranges(M, ins, kInputs, outs, 5)) return rc;
-    const int64_t leaves = leaves_of(M);
     p.cols = static_cast<double *>(workspace_dev);
     p.row_loss = row_loss_dev;
     p.projected = projected_dev;
     if (int rc = launch_rows(call, reinterpret_cast<const void *>(&c51_rows), p, stream)) return rc;
-    LeafArgs l{};
-    l.cols = p.cols; l.partials = p.cols + kCols * M; l.M = M; l.last = leaves == 1; l.loss = loss_out_dev; l.stats = stats_out_dev;
-    if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&c51_leaf), l, leaves, stream)) return rc;
-    if (l.last) return MXV_OK;
-    TreeArgs t{};
-    t.M = M; t.loss = loss_out_dev; t.stats = stats_out_dev;
-    return run_tree(call, reinterpret_cast<const void *>(&c51_tree), kV, t, l.partials, leaves, stream);
+    return sum_columns(call, reinterpret_cast<const void *>(&c51_leaf), reinterpret_cast<const void *>(&c51_tree), p.cols, M, loss_out_dev,
+                       stats_out_dev, stream);
 }
 
 int mxv_c51_loss_backward(void *stream, int64_t M, int32_t A, int32_t Z, const float *logits_dev, int64_t logits_ld, const void *actions_dev,
@@ -452,9 +343,7 @@ int mxv_c51_q_values(void *stream, int64_t M, int32_t A, int32_t Z, const float 
     const CCall call{"mxv_c51_q_values", 'M'};
     if (!logits_dev) return call.bad("%s: logits pointer is NULL", call.api);
     if (!q_out_dev) return call.bad("%s: q_out pointer is NULL", call.api);
-    if (M < 1) return call.bad("%s: M = %lld must be at least 1", call.api, (long long)M);
-    if (M > kMaxElems) return call.bad("%s: M = %lld is beyond 2^40 rows", call.api, (long long)M);
-    if (A < 1 || A > kMaxActions) return call.bad("%s: A = %d must be in 1..%d", call.api, (int)A, kMaxActions);
+    if (int rc = check_counts(call, M, A)) return rc;
     if (int rc = check_support(call, Z, v_min, v_max)) return rc;
     if (int rc = check_rows_ld(call, "logits_ld", logits_ld, M, A, Z)) return rc;
     C51Args p{};

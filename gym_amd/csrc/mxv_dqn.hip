@@ -30,14 +30,19 @@
 #include "mxv_policy_host.hpp"
 #include "mxv_policy_rule.hpp"
 #include "mxv_sum_tree.hpp"
+#include "mxv_value_loss.hpp"
 
 namespace {
 
 using namespace mxv::rule;
 using namespace mxv::policy_host;
 using namespace mxv::sum_tree;
+using namespace mxv::value_loss;
 
-constexpr int kV = MXV_DQN_STATS;    // partials of a leaf: sums of term, ae, qa, y, lin; max ae, min qa, max qa
+// the slots of mxv_value_loss.hpp's partials and finish: sums of term, ae, qa, y, lin; max ae, min qa, max qa
+static_assert(MXV_DQN_STATS == kV && MXV_DQN_LOSS_TERM == 0 && MXV_DQN_TD_ABS_MEAN == 1 && MXV_DQN_Q_TAKEN_MEAN == 2 && MXV_DQN_TARGET_MEAN == 3 &&
+                  MXV_DQN_LINEAR_FRACTION == 4 && MXV_DQN_TD_ABS_MAX == 5 && MXV_DQN_Q_TAKEN_MIN == 6 && MXV_DQN_Q_TAKEN_MAX == 7,
+              "mxv_dqn.h's stats are the slots of mxv_value_loss.hpp");
 
 struct DqnArgs {
     const float *q, *targets, *reward, *next_q, *online, *weights;
@@ -50,21 +55,6 @@ struct DqnArgs {
     double gamma, delta;
     int64_t M, q_ld, next_ld, online_ld, tiles;
     int32_t A, i64;
-};
-
-struct TreeArgs {
-    const double *in;                // [count][8]
-    double *out;                     // [groups][8]; unused by the last level
-    int64_t count, M;
-    int32_t last;
-    float *loss, *stats;
-};
-
-// which of a leaf's partials is a minimum, which a maximum; the others are sums
-struct Partials {
-    static constexpr int V = kV;
-    static constexpr bool is_min(int v) { return v == MXV_DQN_Q_TAKEN_MIN; }
-    static constexpr bool is_max(int v) { return v == MXV_DQN_TD_ABS_MAX || v == MXV_DQN_Q_TAKEN_MAX; }
 };
 
 // ---- one row of the rule ----
@@ -170,26 +160,10 @@ __global__ void __launch_bounds__(kThreads) dqn_leaf(const DqnArgs p) {
     write_partials<Partials>(sm, p.partials);
 }
 
-// ---- forward: one level of the tree; the last one finishes ----
+// ---- forward: one level of the tree; the last one finishes (mxv_value_loss.hpp) ----
 __global__ void __launch_bounds__(kThreads) dqn_tree(const TreeArgs t) {
     __shared__ double sm[kThreads / 64][kV];
-    fold_level<Partials>(sm, t.in, t.count);
-    if (!t.last) {
-        write_partials<Partials>(sm, t.out);
-        return;
-    }
-    if (threadIdx.x != 0) return;
-    const double Mf = (double)t.M;
-    const double loss = four_waves<Add>(sm, MXV_DQN_LOSS_TERM) / Mf;
-    t.loss[0] = to_f32(loss);
-    t.stats[MXV_DQN_LOSS_TERM] = to_f32(loss);
-    t.stats[MXV_DQN_TD_ABS_MEAN] = to_f32(four_waves<Add>(sm, MXV_DQN_TD_ABS_MEAN) / Mf);
-    t.stats[MXV_DQN_Q_TAKEN_MEAN] = to_f32(four_waves<Add>(sm, MXV_DQN_Q_TAKEN_MEAN) / Mf);
-    t.stats[MXV_DQN_TARGET_MEAN] = to_f32(four_waves<Add>(sm, MXV_DQN_TARGET_MEAN) / Mf);
-    t.stats[MXV_DQN_LINEAR_FRACTION] = to_f32(four_waves<Add>(sm, MXV_DQN_LINEAR_FRACTION) / Mf);
-    t.stats[MXV_DQN_TD_ABS_MAX] = to_f32(four_waves<Max>(sm, MXV_DQN_TD_ABS_MAX) + 0.0);      // + 0.0: a zero of either sign leaves as +0.0
-    t.stats[MXV_DQN_Q_TAKEN_MIN] = to_f32(four_waves<Min>(sm, MXV_DQN_Q_TAKEN_MIN) + 0.0);
-    t.stats[MXV_DQN_Q_TAKEN_MAX] = to_f32(four_waves<Max>(sm, MXV_DQN_Q_TAKEN_MAX) + 0.0);
+    tree_level(sm, t);
 }
 
 // ---- backward ----
@@ -264,31 +238,17 @@ int check_rows_ld(const DCall &call, const char *name, int64_t ld, int64_t M, in
     return call.check_stride(ld, M);
 }
 
+constexpr ArgNames kNames = {"q", "targets", "next_q", "next_q_online"};
+
 // what the forward and the backward check alike; fills the inputs of `p`
 int check_loss(const DCall &call, int64_t M, int32_t A, const float *q, int64_t q_ld, const void *actions, int32_t action_bytes,
                const float *targets, const float *reward, const uint8_t *terminated, const float *next_q, int64_t next_q_ld, const float *online,
                int64_t online_ld, double gamma, double delta, const float *weights, DqnArgs &p) {
-    if (!q) return call.bad("%s: q pointer is NULL", call.api);
-    if (!actions) return call.bad("%s: actions pointer is NULL", call.api);
-    if (M < 1) return call.bad("%s: M = %lld must be at least 1", call.api, (long long)M);
-    if (M > kMaxElems) return call.bad("%s: M = %lld is beyond 2^40 rows", call.api, (long long)M);
-    if (A < 1 || A > kMaxActions) return call.bad("%s: A = %d must be in 1..%d", call.api, (int)A, kMaxActions);
-    if (int rc = check_rows_ld(call, "q_ld", q_ld, M, A)) return rc;
-    if (action_bytes != 4 && action_bytes != 8) return call.bad("%s: action_bytes = %d must be 4 (int32) or 8 (int64)", call.api, (int)action_bytes);
-    const bool any_boot = reward || terminated || next_q;
-    if (targets && any_boot)
-        return call.bad("%s: targets is given together with reward, terminated or next_q: exactly one target mode", call.api);
-    if (targets && online) return call.bad("%s: next_q_online is given with targets: it belongs to the bootstrap mode", call.api);
-    if (!targets && !any_boot) return call.bad("%s: neither targets nor reward, terminated and next_q are given: exactly one target mode", call.api);
-    if (!targets) {
-        if (!reward) return call.bad("%s: reward pointer is NULL in the bootstrap mode", call.api);
-        if (!terminated) return call.bad("%s: terminated pointer is NULL in the bootstrap mode", call.api);
-        if (!next_q) return call.bad("%s: next_q pointer is NULL in the bootstrap mode", call.api);
-        if (int rc = check_rows_ld(call, "next_q_ld", next_q_ld, M, A)) return rc;
-        if (online)
-            if (int rc = check_rows_ld(call, "next_q_online_ld", online_ld, M, A)) return rc;
-    }
-    if (!std::isfinite(gamma)) return call.bad("%s: gamma = %g must be finite", call.api, gamma);
+    if (int rc = check_batch(call, kNames, q, actions, M, A)) return rc;
+    const auto check_ld = [&](const char *name, int64_t stride) { return check_rows_ld(call, name, stride, M, A); };
+    if (int rc = check_ld("q_ld", q_ld)) return rc;
+    if (int rc = check_targets(call, kNames, action_bytes, targets, reward, terminated, next_q, next_q_ld, online, online_ld, nullptr, gamma, check_ld))
+        return rc;
     if (!(delta > 0.0)) return call.bad("%s: delta = %g must be above 0 (+Inf: the half squared error)", call.api, delta);
     p.q = q; p.actions = actions; p.targets = targets; p.reward = reward; p.terminated = terminated; p.next_q = next_q; p.online = online;
     p.weights = weights; p.gamma = gamma; p.delta = delta;
@@ -340,9 +300,7 @@ int mxv_dqn_loss(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t
     p.partials = static_cast<double *>(workspace_dev);
     p.td_error = td_error_dev;
     if (int rc = call.launch_blocks(pick<Leaf>(A), p, leaves, stream)) return rc;
-    TreeArgs t{};
-    t.M = M; t.loss = loss_out_dev; t.stats = stats_out_dev;
-    return run_tree(call, reinterpret_cast<const void *>(&dqn_tree), kV, t, p.partials, leaves, stream);
+    return finish_tree(call, reinterpret_cast<const void *>(&dqn_tree), p.partials, leaves, M, loss_out_dev, stats_out_dev, stream);
 }
 
 int mxv_dqn_loss_backward(void *stream, int64_t M, int32_t A, const float *q_dev, int64_t q_ld, const void *actions_dev, int32_t action_bytes,

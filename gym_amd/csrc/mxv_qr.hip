@@ -32,19 +32,21 @@
 #include "mxv_policy_host.hpp"
 #include "mxv_policy_rule.hpp"
 #include "mxv_sum_tree.hpp"
+#include "mxv_value_loss.hpp"
 
 namespace {
 
 using namespace mxv::rule;
 using namespace mxv::policy_host;
 using namespace mxv::sum_tree;
+using namespace mxv::value_loss;
 
-constexpr int kWaves = kThreads / 64;    // rows per tile of qr_rows, qr_bwd and qr_q: one per wave
-constexpr int kV = MXV_QR_STATS;         // partials of a leaf: sums of term, qa, y, ae, cr; max ql, min qa, max qa
-constexpr int kCols = 6;                 // columns a row leaves in the workspace: term, qa, y, ae, cr, ql
 constexpr int kMaxQuantiles = 64;
-constexpr int kGridX = 1 << 16;          // qr_rows, qr_bwd: tiles along x of the grid; beyond, y counts slices of kGridX tiles, and z
-constexpr int kGridY = 1 << 15;          // slices of kGridY of those (2^38 tiles of 2^40 rows fit)
+// the slots of mxv_value_loss.hpp's partials and finish: sums of term, qa, y, ae, cr; max ql, min qa, max qa; a row's columns are term,
+// qa, y, ae, cr, ql
+static_assert(MXV_QR_STATS == kV && MXV_QR_LOSS_TERM == 0 && MXV_QR_Q_TAKEN_MEAN == 1 && MXV_QR_TARGET_MEAN == 2 && MXV_QR_TD_ABS_MEAN == 3 &&
+                  MXV_QR_CROSSING_FRACTION == 4 && MXV_QR_ROW_LOSS_MAX == 5 && MXV_QR_Q_TAKEN_MIN == 6 && MXV_QR_Q_TAKEN_MAX == 7,
+              "mxv_qr.h's stats are the slots of mxv_value_loss.hpp");
 
 struct QrArgs {
     const float *quantiles, *target_quantiles, *reward, *next, *online, *discount, *weights;
@@ -58,22 +60,6 @@ struct QrArgs {
     double gamma, kappa, Nf;         // Nf = (double)N
     int64_t M, ld, next_ld, online_ld, tiles;
     int32_t A, N, i64;
-};
-
-struct LeafArgs {
-    const double *cols;              // [6][M]
-    double *partials;                // [leaves][8]
-    int64_t M;
-    int32_t last;                    // one leaf: finish here
-    float *loss, *stats;
-};
-
-struct TreeArgs {
-    const double *in;                // [count][8]
-    double *out;                     // [groups][8]; unused by the last level
-    int64_t count, M;
-    int32_t last;
-    float *loss, *stats;
 };
 
 // ---- Q of one action: lane k holds quantile k, lanes k >= N the +0.0 slots ----
@@ -161,10 +147,6 @@ __device__ __forceinline__ Row row_of(const QrArgs &p, int64_t i, int k) {
     return w;
 }
 
-__device__ __forceinline__ int wave_of_block() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-// the tile of a workgroup of qr_rows and qr_bwd (grid_rows below)
-__device__ __forceinline__ int64_t tile_of_block() { return ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * kGridX + blockIdx.x; }
-
 // ---- forward: the rows ----
 __global__ void __launch_bounds__(kThreads) qr_rows(const QrArgs p) {
     const int wave = wave_of_block(), lane = threadIdx.x & 63;
@@ -186,69 +168,15 @@ __global__ void __launch_bounds__(kThreads) qr_rows(const QrArgs p) {
     if (p.targets_out && lane < p.N) p.targets_out[i * p.N + lane] = to_f32(w.T);
 }
 
-// ---- forward: the leaves and the tree ----
-// which of a leaf's partials is a minimum, which a maximum; the others are sums
-struct Partials {
-    static constexpr int V = kV;
-    static constexpr bool is_min(int v) { return v == MXV_QR_Q_TAKEN_MIN; }
-    static constexpr bool is_max(int v) { return v == MXV_QR_ROW_LOSS_MAX || v == MXV_QR_Q_TAKEN_MAX; }
-};
-
-// the first lane writes the loss and the diagnostics from the last group's four waves
-__device__ __forceinline__ void finish(const double (*sm)[kV], int64_t M, float *loss_out, float *stats) {
-    const double Mf = (double)M;
-    const double loss = four_waves<Add>(sm, MXV_QR_LOSS_TERM) / Mf;
-    loss_out[0] = to_f32(loss);
-    stats[MXV_QR_LOSS_TERM] = to_f32(loss);
-    stats[MXV_QR_Q_TAKEN_MEAN] = to_f32(four_waves<Add>(sm, MXV_QR_Q_TAKEN_MEAN) / Mf);
-    stats[MXV_QR_TARGET_MEAN] = to_f32(four_waves<Add>(sm, MXV_QR_TARGET_MEAN) / Mf);
-    stats[MXV_QR_TD_ABS_MEAN] = to_f32(four_waves<Add>(sm, MXV_QR_TD_ABS_MEAN) / Mf);
-    stats[MXV_QR_CROSSING_FRACTION] = to_f32(four_waves<Add>(sm, MXV_QR_CROSSING_FRACTION) / Mf);
-    stats[MXV_QR_ROW_LOSS_MAX] = to_f32(four_waves<Max>(sm, MXV_QR_ROW_LOSS_MAX) + 0.0);      // + 0.0: a zero of either sign leaves as +0.0
-    stats[MXV_QR_Q_TAKEN_MIN] = to_f32(four_waves<Min>(sm, MXV_QR_Q_TAKEN_MIN) + 0.0);
-    stats[MXV_QR_Q_TAKEN_MAX] = to_f32(four_waves<Max>(sm, MXV_QR_Q_TAKEN_MAX) + 0.0);
-}
-
+// ---- forward: the leaves and the tree (mxv_value_loss.hpp) ----
 __global__ void __launch_bounds__(kThreads) qr_leaf(const LeafArgs a) {
-    const int tid = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * kLeafRows;
-    double s = 0.0, sq = 0.0, sy = 0.0, se = 0.0, sc = 0.0, mx_l = Max::identity(), mn_q = Min::identity(), mx_q = Max::identity();
-#pragma unroll
-    for (int j = 0; j < kLeafRows / kThreads; ++j) {
-        const int64_t i = row0 + j * kThreads + tid;
-        if (i >= a.M) continue;
-        const double *c = a.cols + i;
-        const double qa = c[a.M], ql = c[5 * a.M];
-        s = s + c[0];
-        sq = sq + qa;
-        sy = sy + c[2 * a.M];
-        se = se + c[3 * a.M];
-        sc = sc + c[4 * a.M];
-        mx_l = ql > mx_l ? ql : mx_l;      // a NaN compares false: skipped
-        mn_q = qa < mn_q ? qa : mn_q;
-        mx_q = qa > mx_q ? qa : mx_q;
-    }
     __shared__ double sm[kThreads / 64][kV];
-    // a batch of one leaf: the one tree level it would pass through adds +0.0 to every sum and nothing else
-    const double zero = a.last ? 0.0 : -0.0;
-    const double t[kV] = {wave_tree<Add>(s) + zero,  wave_tree<Add>(sq) + zero, wave_tree<Add>(sy) + zero, wave_tree<Add>(se) + zero,
-                          wave_tree<Add>(sc) + zero, wave_tree<Max>(mx_l),      wave_tree<Min>(mn_q),      wave_tree<Max>(mx_q)};
-    leave_wave_values(sm, t);
-    if (!a.last) {
-        write_partials<Partials>(sm, a.partials);
-        return;
-    }
-    if (tid == 0) finish(sm, a.M, a.loss, a.stats);
+    leaf_columns(sm, a);
 }
 
 __global__ void __launch_bounds__(kThreads) qr_tree(const TreeArgs t) {
     __shared__ double sm[kThreads / 64][kV];
-    fold_level<Partials>(sm, t.in, t.count);
-    if (!t.last) {
-        write_partials<Partials>(sm, t.out);
-        return;
-    }
-    if (threadIdx.x == 0) finish(sm, t.M, t.loss, t.stats);
+    tree_level(sm, t);
 }
 
 // ---- backward ----
@@ -282,15 +210,9 @@ __global__ void __launch_bounds__(kThreads) qr_q(const QrArgs p) {
 }
 
 // ---- host ----
-// doubles of workspace: the six columns of the rows, the leaves' partials, and every level of the tree that is not the last
-int64_t workspace_doubles(int64_t M) { return kCols * M + workspace_slots(M) * kV; }
-
 using QCall = Call<mxv::QrCall>;
 
-int check_head(const QCall &call, int64_t M, int32_t A, int32_t N) {
-    if (M < 1) return call.bad("%s: M = %lld must be at least 1", call.api, (long long)M);
-    if (M > kMaxElems) return call.bad("%s: M = %lld is beyond 2^40 rows", call.api, (long long)M);
-    if (A < 1 || A > kMaxActions) return call.bad("%s: A = %d must be in 1..%d", call.api, (int)A, kMaxActions);
+int check_quantiles(const QCall &call, int32_t N) {
     if (N < 1 || N > kMaxQuantiles) return call.bad("%s: N = %d must be in 1..%d", call.api, (int)N, kMaxQuantiles);
     return MXV_OK;
 }
@@ -300,33 +222,20 @@ int check_rows_ld(const QCall &call, const char *name, int64_t ld, int64_t M, in
     return call.check_stride(ld, M);
 }
 
+constexpr ArgNames kNames = {"quantiles", "target_quantiles", "next_quantiles", "next_quantiles_online"};
+
 // what the forward and the backward check alike; fills the inputs of `p`
 int check_loss(const QCall &call, int64_t M, int32_t A, int32_t N, const float *quantiles, int64_t ld, const void *actions, int32_t action_bytes,
                const float *target_quantiles, const float *reward, const uint8_t *terminated, const float *next, int64_t next_ld,
                const float *online, int64_t online_ld, double gamma, const float *discount, double kappa, const float *weights, QrArgs &p) {
-    if (!quantiles) return call.bad("%s: quantiles pointer is NULL", call.api);
-    if (!actions) return call.bad("%s: actions pointer is NULL", call.api);
-    if (int rc = check_head(call, M, A, N)) return rc;
+    if (int rc = check_batch(call, kNames, quantiles, actions, M, A)) return rc;
+    if (int rc = check_quantiles(call, N)) return rc;
     if (!std::isfinite(kappa) || !(kappa > 0.0)) return call.bad("%s: kappa = %g must be finite and above 0", call.api, kappa);
-    if (int rc = check_rows_ld(call, "quantiles_ld", ld, M, A, N)) return rc;
-    if (action_bytes != 4 && action_bytes != 8) return call.bad("%s: action_bytes = %d must be 4 (int32) or 8 (int64)", call.api, (int)action_bytes);
-    const bool any_boot = reward || terminated || next;
-    if (target_quantiles && any_boot)
-        return call.bad("%s: target_quantiles is given together with reward, terminated or next_quantiles: exactly one target mode", call.api);
-    if (target_quantiles && online)
-        return call.bad("%s: next_quantiles_online is given with target_quantiles: it belongs to the bootstrap mode", call.api);
-    if (target_quantiles && discount) return call.bad("%s: discount is given with target_quantiles: it belongs to the bootstrap mode", call.api);
-    if (!target_quantiles && !any_boot)
-        return call.bad("%s: neither target_quantiles nor reward, terminated and next_quantiles are given: exactly one target mode", call.api);
-    if (!target_quantiles) {
-        if (!reward) return call.bad("%s: reward pointer is NULL in the bootstrap mode", call.api);
-        if (!terminated) return call.bad("%s: terminated pointer is NULL in the bootstrap mode", call.api);
-        if (!next) return call.bad("%s: next_quantiles pointer is NULL in the bootstrap mode", call.api);
-        if (int rc = check_rows_ld(call, "next_quantiles_ld", next_ld, M, A, N)) return rc;
-        if (online)
-            if (int rc = check_rows_ld(call, "next_quantiles_online_ld", online_ld, M, A, N)) return rc;
-    }
-    if (!std::isfinite(gamma)) return call.bad("%s: gamma = %g must be finite", call.api, gamma);
+    const auto check_ld = [&](const char *name, int64_t stride) { return check_rows_ld(call, name, stride, M, A, N); };
+    if (int rc = check_ld("quantiles_ld", ld)) return rc;
+    if (int rc = check_targets(call, kNames, action_bytes, target_quantiles, reward, terminated, next, next_ld, online, online_ld, discount, gamma,
+                               check_ld))
+        return rc;
     p.quantiles = quantiles; p.actions = actions; p.target_quantiles = target_quantiles; p.reward = reward; p.terminated = terminated;
     p.next = next; p.online = online; p.discount = discount; p.weights = weights; p.gamma = gamma; p.kappa = kappa;
     p.M = M; p.ld = ld; p.next_ld = next_ld; p.online_ld = online_ld; p.tiles = (M + kWaves - 1) / kWaves;
@@ -350,18 +259,6 @@ void input_ranges(const QrArgs &p, const float *g, Range *r) {
     r[7] = {"discount", (uintptr_t)p.discount, mb, 4};
     r[8] = {"weights", (uintptr_t)p.weights, mb, 4};
     r[9] = {"grad_loss", (uintptr_t)g, 4, 4};
-}
-
-// one tile per workgroup; the grid grows along y beyond kGridX tiles and along z beyond kGridX * kGridY
-dim3 grid_rows(int64_t tiles) {
-    const int64_t slices = (tiles + kGridX - 1) / kGridX;
-    return dim3((unsigned)(tiles < kGridX ? tiles : kGridX), (unsigned)(slices < kGridY ? slices : kGridY), (unsigned)((slices + kGridY - 1) / kGridY));
-}
-
-int launch_rows(const QCall &call, const void *kernel, QrArgs &a, void *stream) {
-    void *args[] = {&a};
-    const hipError_t e = hipLaunchKernel(kernel, grid_rows(a.tiles), dim3(kThreads), args, 0, (hipStream_t)stream);
-    return e == hipSuccess ? MXV_OK : call.hip_failed("kernel launch", e);
 }
 
 }  // namespace
@@ -394,18 +291,12 @@ int mxv_qr_loss(void *stream, int64_t M, int32_t A, int32_t N, const float *quan
                           {"loss_out", (uintptr_t)loss_out_dev, 4, 4},
                           {"stats_out", (uintptr_t)stats_out_dev, MXV_QR_STATS * 4, 4}};
     if (int rc = call.check_ranges(M, ins, kInputs, outs, 5)) return rc;
-    const int64_t leaves = leaves_of(M);
     p.cols = static_cast<double *>(workspace_dev);
     p.row_loss = row_loss_dev;
     p.targets_out = targets_out_dev;
     if (int rc = launch_rows(call, reinterpret_cast<const void *>(&qr_rows), p, stream)) return rc;
-    LeafArgs l{};
-    l.cols = p.cols; l.partials = p.cols + kCols * M; l.M = M; l.last = leaves == 1; l.loss = loss_out_dev; l.stats = stats_out_dev;
-    if (int rc = call.launch_blocks(reinterpret_cast<const void *>(&qr_leaf), l, leaves, stream)) return rc;
-    if (l.last) return MXV_OK;
-    TreeArgs t{};
-    t.M = M; t.loss = loss_out_dev; t.stats = stats_out_dev;
-    return run_tree(call, reinterpret_cast<const void *>(&qr_tree), kV, t, l.partials, leaves, stream);
+    return sum_columns(call, reinterpret_cast<const void *>(&qr_leaf), reinterpret_cast<const void *>(&qr_tree), p.cols, M, loss_out_dev,
+                       stats_out_dev, stream);
 }
 
 int mxv_qr_loss_backward(void *stream, int64_t M, int32_t A, int32_t N, const float *quantiles_dev, int64_t quantiles_ld,
@@ -433,7 +324,8 @@ int mxv_qr_q_values(void *stream, int64_t M, int32_t A, int32_t N, const float *
     const QCall call{"mxv_qr_q_values", 'M'};
     if (!quantiles_dev) return call.bad("%s: quantiles pointer is NULL", call.api);
     if (!q_out_dev) return call.bad("%s: q_out pointer is NULL", call.api);
-    if (int rc = check_head(call, M, A, N)) return rc;
+    if (int rc = check_counts(call, M, A)) return rc;
+    if (int rc = check_quantiles(call, N)) return rc;
     if (int rc = check_rows_ld(call, "quantiles_ld", quantiles_ld, M, A, N)) return rc;
     QrArgs p{};
     p.quantiles = quantiles_dev; p.ld = quantiles_ld; p.M = M; p.A = A; p.N = N; p.Nf = (double)N; p.q_out = q_out_dev;

@@ -20,9 +20,9 @@ import math
 
 from . import _native
 from ._policy_args import LEAF_ROWS       # rows per leaf of the sum tree, and leaves per group of a level
-from ._policy_args import MAX_ACTIONS, _ld, _one_device, _ptr, _rows, _tree_launches, _vector
-from ._policy_args import _check as _raise
-from ._policy_args import _workspace as _shared_workspace
+from ._policy_args import MAX_ACTIONS, _ld, _ptr, _rows, _vector
+from ._value_loss import Bound, _finish, _make_function, _target_mode
+from ._value_loss import _no_grad_input      # noqa: F401  (gym_amd.c51 and gym_amd.qr took it from here)
 from .returns import _scalar
 
 DQN_EXPORTS = ("mxv_dqn_workspace_bytes", "mxv_dqn_loss", "mxv_dqn_loss_backward", "mxv_dqn_last_error")
@@ -34,41 +34,8 @@ STAT_NAMES = ("loss_term", "td_abs_mean", "q_taken_mean", "target_mean", "linear
 lib = _native.lib
 _P, _D, _I64, _I32 = C.c_void_p, C.c_double, C.c_int64, C.c_int32
 _INPUTS = [_P, _I64, _I32, _P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P, _I64, _D, _D, _P]      # stream .. weights
-lib.mxv_dqn_workspace_bytes.argtypes = [_I64]
-lib.mxv_dqn_workspace_bytes.restype = _I64
-lib.mxv_dqn_loss.argtypes = _INPUTS + [_P, _I64, _P, _P, _P]
-lib.mxv_dqn_loss.restype = C.c_int
-lib.mxv_dqn_loss_backward.argtypes = _INPUTS + [_P, _P]
-lib.mxv_dqn_loss_backward.restype = C.c_int
-lib.mxv_dqn_last_error.argtypes = []
-lib.mxv_dqn_last_error.restype = C.c_char_p
-
-
-def _check(rc: int):
-    _raise(rc, lib.mxv_dqn_last_error)
-
-
-def workspace_bytes(rows: int) -> int:
-    """Bytes of `workspace=` that a batch of `rows` rows needs (the partial sums of its leaves)."""
-    n = int(lib.mxv_dqn_workspace_bytes(int(rows)))
-    if n == 0:
-        raise ValueError(f"rows must be in 1..2^40, got {rows!r}")
-    return n
-
-
-def launches(rows: int) -> int:
-    """Kernel launches of one forward on `rows` rows: the leaves, then one per level of the tree.  The backward is always one."""
-    workspace_bytes(rows)
-    return _tree_launches(rows)
-
-
-def _workspace(t, workspace, M, dev):
-    return _shared_workspace(t, workspace, M, dev, workspace_bytes(M), "dqn")
-
-
-def _no_grad_input(t, x, name):
-    if x is not None and t.is_grad_enabled() and x.requires_grad:
-        raise ValueError(f"{name} must not require grad: the loss is differentiable with respect to q alone")
+_BOUND = Bound(lib, "mxv_dqn", _INPUTS, [_P, _I64, _P, _P, _P], stats=STATS)      # the workspace, its bytes, td_error, loss, stats
+_check, workspace_bytes, launches, _workspace = _BOUND.check, _BOUND.workspace_bytes, _BOUND.launches, _BOUND.workspace
 
 
 def _delta(delta):
@@ -88,19 +55,17 @@ def _delta(delta):
 class _Inputs:
     """The checked inputs of one call, as the C entry points take them."""
 
-    TENSORS = ("q", "act", "targets", "reward", "term", "next_q", "online", "weights")
+    TENSORS = ("q", "act", "targets", "reward", "term", "next", "online", "weights")
     SCALARS = ("M", "A", "gamma", "delta", "dev")
 
     def call_args(self, t):
         s = self
         return (t.cuda.current_stream(s.dev).cuda_stream, s.M, s.A, s.q.data_ptr(), _ld(s.q, s.A), s.act.data_ptr(), s.act.element_size(),
-                _ptr(s.targets), _ptr(s.reward), _ptr(s.term), _ptr(s.next_q), 0 if s.next_q is None else _ld(s.next_q, s.A), _ptr(s.online),
+                _ptr(s.targets), _ptr(s.reward), _ptr(s.term), _ptr(s.next), 0 if s.next is None else _ld(s.next, s.A), _ptr(s.online),
                 0 if s.online is None else _ld(s.online, s.A), s.gamma, s.delta, _ptr(s.weights))
 
-
-def _forward(t, a, ws, ws_bytes, td, loss, stats):
-    with t.cuda.device(a.dev):
-        _check(lib.mxv_dqn_loss(*a.call_args(t), ws.data_ptr(), ws_bytes, _ptr(td), loss.data_ptr(), stats.data_ptr()))
+    def grad_shape(self):
+        return self.M, self.A
 
 
 _FUNCTION = None
@@ -109,39 +74,8 @@ _FUNCTION = None
 def _function():
     """The torch.autograd.Function, made at the first differentiable call: importing this module does not import torch."""
     global _FUNCTION
-    if _FUNCTION is not None:
-        return _FUNCTION
-    import torch as t
-    from torch.autograd.function import once_differentiable
-
-    class DqnLoss(t.autograd.Function):
-        @staticmethod
-        def forward(ctx, q, a, td):
-            ctx.set_materialize_grads(False)
-            loss = t.empty((), dtype=t.float32, device=a.dev)
-            stats = t.empty(STATS, dtype=t.float32, device=a.dev)
-            ws, ws_bytes = _workspace(t, None, a.M, a.dev)
-            _forward(t, a, ws, ws_bytes, td, loss, stats)
-            ctx.save_for_backward(*(getattr(a, k) for k in a.TENSORS))      # the inputs alone: the backward recomputes the rows
-            ctx.scalars = tuple(getattr(a, k) for k in a.SCALARS)
-            ctx.mark_non_differentiable(stats)
-            return loss, stats
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, g_loss, _g_stats):
-            if g_loss is None or not ctx.needs_input_grad[0]:
-                return None, None, None
-            a = _Inputs()
-            for k, v in zip(a.TENSORS + a.SCALARS, ctx.saved_tensors + ctx.scalars):
-                setattr(a, k, v)
-            g = g_loss.contiguous()      # one float32 in device memory: read by the kernel, never by the host
-            grad = t.empty((a.M, a.A), dtype=t.float32, device=a.dev)      # contiguous; every element is written
-            with t.cuda.device(a.dev):
-                _check(lib.mxv_dqn_loss_backward(*a.call_args(t), g.data_ptr(), grad.data_ptr()))
-            return grad, None, None
-
-    _FUNCTION = DqnLoss
+    if _FUNCTION is None:
+        _FUNCTION = _make_function("DqnLoss", _Inputs, _BOUND)
     return _FUNCTION
 
 
@@ -178,59 +112,12 @@ def dqn_loss(q, actions, *, targets=None, reward=None, terminated=None, next_q=N
     lead = q.shape[:-1]
     a.M, a.A = a.q.shape
     a.act = _vector(t, actions, "actions", lead, (t.int64, t.int32))
-    boot = {"reward": reward, "terminated": terminated, "next_q": next_q}
-    if targets is not None:
-        given = [k for k, v in boot.items() if v is not None]
-        if given:
-            raise ValueError(f"targets is given together with {', '.join(given)}: exactly one target mode")
-        if next_q_online is not None:
-            raise ValueError("next_q_online is given with targets: it belongs to the bootstrap mode (reward, terminated, next_q)")
-    else:
-        missing = [k for k, v in boot.items() if v is None]
-        if len(missing) == 3:
-            raise ValueError("neither targets nor reward, terminated and next_q are given: exactly one target mode")
-        if missing:
-            raise ValueError(f"the bootstrap mode needs reward, terminated and next_q: {', '.join(missing)} missing")
+    a.reward, a.term, a.next, a.online = _target_mode(t, _rows, lead, ("q", q), ("targets", targets),
+                                                      {"reward": reward, "terminated": terminated, "next_q": next_q},
+                                                      ("next_q_online", next_q_online), rows_args=(MAX_ACTIONS, what))
     a.targets = None if targets is None else _vector(t, targets, "targets", lead, f32)
-    a.reward = None if reward is None else _vector(t, reward, "reward", lead, f32)
-    if isinstance(terminated, t.Tensor) and terminated.dtype == t.bool:
-        terminated = terminated.view(t.uint8)
-    a.term = None if terminated is None else _vector(t, terminated, "terminated", lead, (t.uint8,))
-    a.next_q = a.online = None
-    for name, x in (("next_q", next_q), ("next_q_online", next_q_online)):
-        if x is None:
-            continue
-        x2 = _rows(t, x, name, MAX_ACTIONS, what)
-        if tuple(x.shape) != tuple(q.shape):
-            raise ValueError(f"{name} must have shape {tuple(q.shape)} like q, got {tuple(x.shape)}")
-        setattr(a, "next_q" if name == "next_q" else "online", x2)
     a.weights = None if weights is None else _vector(t, weights, "weights", lead, f32)
     a.gamma, a.delta = _scalar("gamma", gamma), _delta(delta)
     td = None if td_error is None else _vector(t, td_error, "td_error", lead, f32)
-    for x, name in ((actions, "actions"), (targets, "targets"), (reward, "reward"), (next_q, "next_q"), (next_q_online, "next_q_online"),
-                    (weights, "weights"), (td_error, "td_error")):
-        _no_grad_input(t, x, name)
-    grads = t.is_grad_enabled() and q.requires_grad
-    loss = stats = None
-    if out is not None or workspace is not None:
-        if grads:
-            raise ValueError("out= and workspace= cannot be used when q requires grad: autograd owns the outputs")
-    if out is not None:
-        out = tuple(out)
-        if len(out) != 2:
-            raise ValueError(f"out must hold 2 entries (loss, stats), got {len(out)}")
-        loss = _vector(t, out[0], "out (loss)", (), f32)
-        stats = _vector(t, out[1], "out (stats)", (STATS,), f32)
-    a.dev = _one_device((("q", a.q), ("actions", a.act), ("targets", a.targets), ("reward", a.reward), ("terminated", a.term),
-                         ("next_q", a.next_q), ("next_q_online", a.online), ("weights", a.weights), ("td_error", td), ("out (loss)", loss),
-                         ("out (stats)", stats), ("workspace", workspace if isinstance(workspace, t.Tensor) else None)))
-    if grads:
-        q_rows, a.q = a.q, a.q.detach()
-        return _function().apply(q_rows, a, td)
-    a.q = a.q.detach()
-    ws, ws_bytes = _workspace(t, workspace, a.M, a.dev)
-    if out is None:
-        loss = t.empty((), dtype=t.float32, device=a.dev)
-        stats = t.empty(STATS, dtype=t.float32, device=a.dev)
-    _forward(t, a, ws, ws_bytes, td, loss, stats)
-    return out if out is not None else (loss, stats)
+    return _finish(t, _BOUND, _function, a, [("q", a.q), ("actions", a.act), ("targets", a.targets), ("reward", a.reward), ("terminated", a.term),
+                                             ("next_q", a.next), ("next_q_online", a.online), ("weights", a.weights), ("td_error", td)], workspace, out)

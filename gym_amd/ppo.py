@@ -19,9 +19,8 @@ import ctypes as C
 
 from . import _native
 from ._policy_args import LEAF_ROWS       # rows per leaf of the sum tree, and leaves per group of a level
-from ._policy_args import _check as _raise
-from ._policy_args import _one_device, _ptr, _tree_launches, _vector
-from ._policy_args import _workspace as _shared_workspace
+from ._policy_args import _one_device, _ptr, _vector
+from ._value_loss import Bound, _outputs
 from .returns import _scalar
 
 PPO_EXPORTS = ("mxv_ppo_workspace_bytes", "mxv_ppo_advantage_moments", "mxv_ppo_clip_loss", "mxv_ppo_clip_loss_backward", "mxv_ppo_last_error")
@@ -32,38 +31,14 @@ STAT_NAMES = ("policy_loss", "value_loss", "entropy", "approx_kl", "approx_kl3",
 
 lib = _native.lib
 _P, _D, _I64 = C.c_void_p, C.c_double, C.c_int64
-lib.mxv_ppo_workspace_bytes.argtypes = [_I64]
-lib.mxv_ppo_workspace_bytes.restype = _I64
+_BOUND = Bound(lib, "mxv_ppo", stats=STATS)
+_check, workspace_bytes, launches, _workspace = _BOUND.check, _BOUND.workspace_bytes, _BOUND.launches, _BOUND.workspace
 lib.mxv_ppo_advantage_moments.argtypes = [_P, _I64, _P, _D, _P, _I64, _P]
 lib.mxv_ppo_advantage_moments.restype = C.c_int
 lib.mxv_ppo_clip_loss.argtypes = [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _P, _I64, _P, _P]
 lib.mxv_ppo_clip_loss.restype = C.c_int
 lib.mxv_ppo_clip_loss_backward.argtypes = [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P]
 lib.mxv_ppo_clip_loss_backward.restype = C.c_int
-lib.mxv_ppo_last_error.argtypes = []
-lib.mxv_ppo_last_error.restype = C.c_char_p
-
-
-def _check(rc: int):
-    _raise(rc, lib.mxv_ppo_last_error)
-
-
-def workspace_bytes(rows: int) -> int:
-    """Bytes of `workspace=` that a batch of `rows` rows needs (the partial sums of its leaves)."""
-    n = int(lib.mxv_ppo_workspace_bytes(int(rows)))
-    if n == 0:
-        raise ValueError(f"rows must be in 1..2^40, got {rows!r}")
-    return n
-
-
-def launches(rows: int) -> int:
-    """Kernel launches of one forward (and of advantage_moments) on `rows` rows: the leaves, then one per level of the tree."""
-    workspace_bytes(rows)
-    return _tree_launches(rows)
-
-
-def _workspace(t, workspace, M, dev):
-    return _shared_workspace(t, workspace, M, dev, workspace_bytes(M), "ppo")
 
 
 def _no_grad_input(t, x, name):
@@ -200,16 +175,7 @@ def ppo_clip_loss(log_prob, old_log_prob, advantages, *, clip=0.2, moments=None,
     for x, name in ((old_log_prob, "old_log_prob"), (advantages, "advantages"), (returns, "returns"), (moments, "moments")):
         _no_grad_input(t, x, name)
     grads = t.is_grad_enabled() and any(x is not None and x.requires_grad for x in (log_prob, entropy, values))
-    loss = stats = None
-    if out is not None or workspace is not None:
-        if grads:
-            raise ValueError("out= and workspace= cannot be used when an input requires grad: autograd owns the outputs")
-    if out is not None:
-        out = tuple(out)
-        if len(out) != 2:
-            raise ValueError(f"out must hold 2 entries (loss, stats), got {len(out)}")
-        loss = _vector(t, out[0], "out (loss)", (), f32)
-        stats = _vector(t, out[1], "out (stats)", (STATS,), f32)
+    out, loss, stats = _outputs(t, out, workspace, grads, "an input", STATS)
     dev = _one_device((("log_prob", lp), ("old_log_prob", old), ("advantages", adv), ("moments", mom), ("entropy", en), ("values", val),
                        ("returns", ret), ("out (loss)", loss), ("out (stats)", stats),
                        ("workspace", workspace if isinstance(workspace, t.Tensor) else None)))

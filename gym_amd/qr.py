@@ -24,10 +24,8 @@ import ctypes as C
 
 from . import _native
 from ._policy_args import LEAF_ROWS       # rows per leaf of the sum tree, and leaves per group of a level (kLeafRows, kTreeFan)
-from ._policy_args import MAX_ACTIONS, _one_device, _ptr, _tree_launches, _vector
-from ._policy_args import _check as _raise
-from ._policy_args import _workspace as _shared_workspace
-from .dqn import _no_grad_input
+from ._policy_args import _one_device, _ptr, _vector
+from ._value_loss import Bound, _finish, _heads_checker, _ld3, _make_function, _no_grad_input, _target_mode
 from .returns import _scalar
 
 QR_EXPORTS = ("mxv_qr_workspace_bytes", "mxv_qr_loss", "mxv_qr_loss_backward", "mxv_qr_q_values", "mxv_qr_last_error")
@@ -44,70 +42,13 @@ MAX_BLOCKS = 2048       # workgroups of quantile_q_values, which stride over its
 lib = _native.lib
 _P, _D, _I64, _I32 = C.c_void_p, C.c_double, C.c_int64, C.c_int32
 _INPUTS = [_P, _I64, _I32, _I32, _P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P, _I64, _D, _P, _D, _P]      # stream .. weights
-lib.mxv_qr_workspace_bytes.argtypes = [_I64]
-lib.mxv_qr_workspace_bytes.restype = _I64
-lib.mxv_qr_loss.argtypes = _INPUTS + [_P, _I64, _P, _P, _P, _P]
-lib.mxv_qr_loss.restype = C.c_int
-lib.mxv_qr_loss_backward.argtypes = _INPUTS + [_P, _P]
-lib.mxv_qr_loss_backward.restype = C.c_int
+_BOUND = Bound(lib, "mxv_qr", _INPUTS, [_P, _I64, _P, _P, _P, _P], leaf_finishes=True, stats=STATS)      # .. row_loss, targets_out, loss, stats
+_check, workspace_bytes, launches, _workspace = _BOUND.check, _BOUND.workspace_bytes, _BOUND.launches, _BOUND.workspace
 lib.mxv_qr_q_values.argtypes = [_P, _I64, _I32, _I32, _P, _I64, _P]
 lib.mxv_qr_q_values.restype = C.c_int
-lib.mxv_qr_last_error.argtypes = []
-lib.mxv_qr_last_error.restype = C.c_char_p
 
 
-def _check(rc: int):
-    _raise(rc, lib.mxv_qr_last_error)
-
-
-def workspace_bytes(rows: int) -> int:
-    """Bytes of `workspace=` that a batch of `rows` rows needs (six float64 per row, and the partial sums of the leaves)."""
-    n = int(lib.mxv_qr_workspace_bytes(int(rows)))
-    if n == 0:
-        raise ValueError(f"rows must be in 1..2^40, got {rows!r}")
-    return n
-
-
-def launches(rows: int) -> int:
-    """Kernel launches of one forward on `rows` rows: the rows, the leaves (which finish a batch of one leaf), then one per level of the
-    tree: 2 up to 1024 rows, 3 up to 2^20, 4 up to 2^30.  The backward and quantile_q_values are always one."""
-    workspace_bytes(rows)
-    return 2 if int(rows) <= LEAF_ROWS else 1 + _tree_launches(rows)
-
-
-def _workspace(t, workspace, M, dev):
-    return _shared_workspace(t, workspace, M, dev, workspace_bytes(M), "qr")
-
-
-def _heads(t, x, name):
-    """A float32 [..., A, N] tensor as its [M, A, N] rows: the last two dims contiguous; 3-D tensors may have strided rows (views into
-    wider buffers), more dims must flatten without a copy."""
-    what = f"[..., A, N] with at least one row, 1 <= A <= {MAX_ACTIONS} and 1 <= N <= {MAX_QUANTILES}"
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype != t.float32:
-        raise ValueError(f"{name} must be torch.float32, got {x.dtype}")
-    if x.dim() < 3 or x.numel() == 0 or not 1 <= x.shape[-2] <= MAX_ACTIONS or not 1 <= x.shape[-1] <= MAX_QUANTILES:
-        raise ValueError(f"{name} must have shape {what}, got {tuple(x.shape)}")
-    A, N = x.shape[-2:]
-    if x.dim() == 3:
-        x3 = x
-    else:
-        try:
-            x3 = x.view(-1, A, N)
-        except RuntimeError:
-            raise ValueError(f"{name} of shape {tuple(x.shape)} with strides {tuple(x.stride())} cannot be viewed as [M, {A}, {N}] rows "
-                             f"(view(-1, {A}, {N}) fails): pass a contiguous tensor") from None
-    if (N > 1 and x3.stride(2) != 1) or (A > 1 and x3.stride(1) != N):
-        raise ValueError(f"{name} must be contiguous in its last two dimensions (strides {tuple(x3.stride())}): rows may be strided "
-                         "views, actions and quantiles not")
-    if x3.shape[0] > 1 and x3.stride(0) < A * N:
-        raise ValueError(f"{name} has row stride {x3.stride(0)} < {A * N}: rows overlap")
-    return x3
-
-
-def _ld3(x3):
-    return x3.stride(0) if x3.shape[0] > 1 else x3.shape[1] * x3.shape[2]
+_heads = _heads_checker("N", 1, MAX_QUANTILES, "quantiles")      # _heads(t, x, name): a float32 [..., A, N] tensor as its [M, A, N] rows
 
 
 def _kappa(kappa):
@@ -129,10 +70,8 @@ class _Inputs:
                 s.act.element_size(), _ptr(s.target_quantiles), _ptr(s.reward), _ptr(s.term), _ptr(s.next), 0 if s.next is None else _ld3(s.next),
                 _ptr(s.online), 0 if s.online is None else _ld3(s.online), s.gamma, _ptr(s.discount), s.kappa, _ptr(s.weights))
 
-
-def _forward(t, a, ws, ws_bytes, row_loss, targets_out, loss, stats):
-    with t.cuda.device(a.dev):
-        _check(lib.mxv_qr_loss(*a.call_args(t), ws.data_ptr(), ws_bytes, _ptr(row_loss), _ptr(targets_out), loss.data_ptr(), stats.data_ptr()))
+    def grad_shape(self):
+        return self.M, self.A, self.N
 
 
 _FUNCTION = None
@@ -141,39 +80,8 @@ _FUNCTION = None
 def _function():
     """The torch.autograd.Function, made at the first differentiable call: importing this module does not import torch."""
     global _FUNCTION
-    if _FUNCTION is not None:
-        return _FUNCTION
-    import torch as t
-    from torch.autograd.function import once_differentiable
-
-    class QuantileDqnLoss(t.autograd.Function):
-        @staticmethod
-        def forward(ctx, quantiles, a, row_loss, targets_out):
-            ctx.set_materialize_grads(False)
-            loss = t.empty((), dtype=t.float32, device=a.dev)
-            stats = t.empty(STATS, dtype=t.float32, device=a.dev)
-            ws, ws_bytes = _workspace(t, None, a.M, a.dev)
-            _forward(t, a, ws, ws_bytes, row_loss, targets_out, loss, stats)
-            ctx.save_for_backward(*(getattr(a, k) for k in a.TENSORS))      # the inputs alone: the backward recomputes the rows
-            ctx.scalars = tuple(getattr(a, k) for k in a.SCALARS)
-            ctx.mark_non_differentiable(stats)
-            return loss, stats
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, g_loss, _g_stats):
-            if g_loss is None or not ctx.needs_input_grad[0]:
-                return None, None, None, None
-            a = _Inputs()
-            for k, v in zip(a.TENSORS + a.SCALARS, ctx.saved_tensors + ctx.scalars):
-                setattr(a, k, v)
-            g = g_loss.contiguous()      # one float32 in device memory: read by the kernel, never by the host
-            grad = t.empty((a.M, a.A, a.N), dtype=t.float32, device=a.dev)      # contiguous; every element is written
-            with t.cuda.device(a.dev):
-                _check(lib.mxv_qr_loss_backward(*a.call_args(t), g.data_ptr(), grad.data_ptr()))
-            return grad, None, None, None
-
-    _FUNCTION = QuantileDqnLoss
+    if _FUNCTION is None:
+        _FUNCTION = _make_function("QuantileDqnLoss", _Inputs, _BOUND)
     return _FUNCTION
 
 
@@ -219,70 +127,22 @@ def quantile_dqn_loss(quantiles, actions, *, target_quantiles=None, reward=None,
     lead = quantiles.shape[:-2]
     a.M, a.A, a.N = a.quantiles.shape
     a.act = _vector(t, actions, "actions", lead, (t.int64, t.int32))
-    boot = {"reward": reward, "terminated": terminated, "next_quantiles": next_quantiles}
     if gamma is not None and discount is not None:
         raise ValueError("gamma and discount are both given: the bootstrap takes the scalar or the per-row one")
-    if target_quantiles is not None:
-        given = [k for k, v in boot.items() if v is not None]
-        if given:
-            raise ValueError(f"target_quantiles is given together with {', '.join(given)}: exactly one target mode")
-        for name, x in (("next_quantiles_online", next_quantiles_online), ("discount", discount)):
-            if x is not None:
-                raise ValueError(f"{name} is given with target_quantiles: it belongs to the bootstrap mode (reward, terminated, next_quantiles)")
-    else:
-        missing = [k for k, v in boot.items() if v is None]
-        if len(missing) == 3:
-            raise ValueError("neither target_quantiles nor reward, terminated and next_quantiles are given: exactly one target mode")
-        if missing:
-            raise ValueError(f"the bootstrap mode needs reward, terminated and next_quantiles: {', '.join(missing)} missing")
+    a.reward, a.term, a.next, a.online = _target_mode(t, _heads, lead, ("quantiles", quantiles), ("target_quantiles", target_quantiles),
+                                                      {"reward": reward, "terminated": terminated, "next_quantiles": next_quantiles},
+                                                      ("next_quantiles_online", next_quantiles_online), (("discount", discount),))
     a.target_quantiles = None if target_quantiles is None else _vector(t, target_quantiles, "target_quantiles", tuple(lead) + (a.N,), f32)
-    a.reward = None if reward is None else _vector(t, reward, "reward", lead, f32)
-    if isinstance(terminated, t.Tensor) and terminated.dtype == t.bool:
-        terminated = terminated.view(t.uint8)
-    a.term = None if terminated is None else _vector(t, terminated, "terminated", lead, (t.uint8,))
-    a.next = a.online = None
-    for name, x in (("next_quantiles", next_quantiles), ("next_quantiles_online", next_quantiles_online)):
-        if x is None:
-            continue
-        x3 = _heads(t, x, name)
-        if tuple(x.shape) != tuple(quantiles.shape):
-            raise ValueError(f"{name} must have shape {tuple(quantiles.shape)} like quantiles, got {tuple(x.shape)}")
-        setattr(a, "next" if name == "next_quantiles" else "online", x3)
     a.discount = None if discount is None else _vector(t, discount, "discount", lead, f32)
     a.weights = None if weights is None else _vector(t, weights, "weights", lead, f32)
     a.gamma = 0.0 if discount is not None else _scalar("gamma", 0.99 if gamma is None else gamma)      # not read beside a discount
     a.kappa = _kappa(kappa)
     rl = None if row_loss is None else _vector(t, row_loss, "row_loss", lead, f32)
     to = None if targets_out is None else _vector(t, targets_out, "targets_out", tuple(lead) + (a.N,), f32)
-    for x, name in ((actions, "actions"), (target_quantiles, "target_quantiles"), (reward, "reward"), (next_quantiles, "next_quantiles"),
-                    (next_quantiles_online, "next_quantiles_online"), (discount, "discount"), (weights, "weights"), (row_loss, "row_loss"),
-                    (targets_out, "targets_out")):
-        _no_grad_input(t, x, name)
-    grads = t.is_grad_enabled() and quantiles.requires_grad
-    loss = stats = None
-    if out is not None or workspace is not None:
-        if grads:
-            raise ValueError("out= and workspace= cannot be used when quantiles requires grad: autograd owns the outputs")
-    if out is not None:
-        out = tuple(out)
-        if len(out) != 2:
-            raise ValueError(f"out must hold 2 entries (loss, stats), got {len(out)}")
-        loss = _vector(t, out[0], "out (loss)", (), f32)
-        stats = _vector(t, out[1], "out (stats)", (STATS,), f32)
-    a.dev = _one_device((("quantiles", a.quantiles), ("actions", a.act), ("target_quantiles", a.target_quantiles), ("reward", a.reward),
-                         ("terminated", a.term), ("next_quantiles", a.next), ("next_quantiles_online", a.online), ("discount", a.discount),
-                         ("weights", a.weights), ("row_loss", rl), ("targets_out", to), ("out (loss)", loss), ("out (stats)", stats),
-                         ("workspace", workspace if isinstance(workspace, t.Tensor) else None)))
-    if grads:
-        rows, a.quantiles = a.quantiles, a.quantiles.detach()
-        return _function().apply(rows, a, rl, to)
-    a.quantiles = a.quantiles.detach()
-    ws, ws_bytes = _workspace(t, workspace, a.M, a.dev)
-    if out is None:
-        loss = t.empty((), dtype=t.float32, device=a.dev)
-        stats = t.empty(STATS, dtype=t.float32, device=a.dev)
-    _forward(t, a, ws, ws_bytes, rl, to, loss, stats)
-    return out if out is not None else (loss, stats)
+    return _finish(t, _BOUND, _function, a, [("quantiles", a.quantiles), ("actions", a.act), ("target_quantiles", a.target_quantiles),
+                                             ("reward", a.reward), ("terminated", a.term), ("next_quantiles", a.next),
+                                             ("next_quantiles_online", a.online), ("discount", a.discount), ("weights", a.weights),
+                                             ("row_loss", rl), ("targets_out", to)], workspace, out)
 
 
 def quantile_q_values(quantiles, out=None):

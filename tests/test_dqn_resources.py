@@ -16,7 +16,7 @@ import tempfile
 import pytest
 
 from conftest import ROOT
-from test_c51_resources import TREE_COPIES, barriers, tree_header
+from test_c51_resources import TREE_COPIES, VALUE_COPIES, barriers, tree_header, value_header
 from test_policy_eval_resources import HIPCC, _resources
 
 SRC = os.path.join(ROOT, "gym_amd", "csrc", "mxv_dqn.hip")
@@ -30,7 +30,7 @@ BUDGET = {
     LEAF % 4: (8, 40, COMBINE_LDS),                                   # 34
     LEAF % 6: (8, 40, COMBINE_LDS),                                   # 34
     LEAF % 0: (8, 40, COMBINE_LDS),                                   # 34
-    "_ZN12_GLOBAL__N_18dqn_treeENS_8TreeArgsE": (8, 48, COMBINE_LDS),  # 45
+    "_ZN12_GLOBAL__N_18dqn_treeEN3mxv10value_loss8TreeArgsE": (8, 48, COMBINE_LDS),  # 45
     BWD % 2: (8, 32, 0),                                              # 26
     BWD % 3: (8, 32, 0),                                              # 28
     BWD % 4: (8, 32, 0),                                              # 30
@@ -67,10 +67,13 @@ def test_every_kernel_stays_in_registers_and_the_lds_is_the_combine_and_the_stag
 
 def test_the_source_shares_the_rule_and_the_host_checks():
     src = re.sub(r"//.*", "", open(SRC).read())
-    assert '#include "mxv_policy_rule.hpp"' in src and '#include "mxv_policy_host.hpp"' in src and "kThreads" in src and "kMaxActions" in src
-    assert '#include "mxv_sum_tree.hpp"' in src and "wave_tree<" in src and "run_tree(" in src
+    value = value_header()      # the limits of a batch and the levels of the tree are used there
+    assert '#include "mxv_policy_rule.hpp"' in src and '#include "mxv_policy_host.hpp"' in src and "kThreads" in src and "kMaxActions" in value
+    assert '#include "mxv_sum_tree.hpp"' in src and "wave_tree<" in src and "run_tree(" in value
+    assert '#include "mxv_value_loss.hpp"' in src and "check_batch(" in src and "check_targets(" in src and "finish_tree(" in src
+    assert "write_partials<Partials>(" in src and "static_assert(MXV_DQN_STATS == kV" in src      # its own leaf writes the shared partials
     assert "Call<mxv::DqnCall>" in src and "check_ranges(" in src and "check_stride(" in src
-    for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b") + TREE_COPIES:
+    for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b") + TREE_COPIES + VALUE_COPIES:
         assert not re.search(copy, src), copy
     for word in ("atomic", "asm", "__shfl"):
         assert word not in src, word

@@ -16,7 +16,7 @@ import pytest
 
 from conftest import ROOT
 from policy_host import RULE_NAMES
-from test_c51_resources import COMBINE_LDS, TREE, TREE_COPIES, barriers, tree_header
+from test_c51_resources import COMBINE_LDS, TREE, TREE_COPIES, VALUE, VALUE_COPIES, barriers, tree_header, value_header
 from test_policy_eval_resources import HIPCC, _resources
 
 CSRC = os.path.join(ROOT, "gym_amd", "csrc")
@@ -26,8 +26,8 @@ KERNELS = ("qr_rows", "qr_leaf", "qr_tree", "qr_bwd", "qr_q")
 # symbol: (waves per SIMD, VGPR bound, LDS bytes) as reported at the time of the change; reported VGPRs in the comments
 BUDGET = {
     "_ZN12_GLOBAL__N_17qr_rowsENS_6QrArgsE": (8, 40, 0),                # 34
-    "_ZN12_GLOBAL__N_17qr_leafENS_8LeafArgsE": (8, 48, COMBINE_LDS),    # 45
-    "_ZN12_GLOBAL__N_17qr_treeENS_8TreeArgsE": (8, 48, COMBINE_LDS),    # 45
+    "_ZN12_GLOBAL__N_17qr_leafEN3mxv10value_loss8LeafArgsE": (8, 48, COMBINE_LDS),    # 45
+    "_ZN12_GLOBAL__N_17qr_treeEN3mxv10value_loss8TreeArgsE": (8, 48, COMBINE_LDS),    # 45
     "_ZN12_GLOBAL__N_16qr_bwdENS_6QrArgsE": (8, 32, 0),                 # 28
     "_ZN12_GLOBAL__N_14qr_qENS_6QrArgsE": (8, 24, 0),                   # 18
 }
@@ -68,15 +68,17 @@ def test_every_kernel_stays_in_registers_and_the_only_lds_is_the_combine(remarks
 
 def test_the_source_shares_the_rule_the_tree_and_the_host_checks():
     src = re.sub(r"//.*", "", open(SRC).read())
-    for header in ("mxv_policy_rule.hpp", "mxv_policy_host.hpp", "mxv_sum_tree.hpp"):
+    for header in ("mxv_policy_rule.hpp", "mxv_policy_host.hpp", "mxv_sum_tree.hpp", "mxv_value_loss.hpp"):
         assert f'#include "{header}"' in src, header
-    assert "kThreads" in src and "kMaxActions" in src and "kMaxBlocks" not in src      # qr_q strides through Call::launch's grid_of
+    value = value_header()      # the limits of a batch, the levels of the tree and the fold of a level are used there
+    assert "kThreads" in src and "kMaxActions" in value and "kMaxBlocks" not in src      # qr_q strides through Call::launch's grid_of
     assert "Call<mxv::QrCall>" in src and "check_ranges(" in src and "check_stride(" in src and "check_workspace(" in src
     for copy in (r"\bkThreads\s*=", r"\bkMaxActions\s*=", r"\bkMaxElems\s*=", r"\bkMaxBlocks\s*=", r"struct\s+Range\b", r"\bint\s+check_ranges\b",
-                 r"\bint\s+check_workspace\b", r"\bdouble\s+(exp_rule|log_rule|e_of)\b", r"\b(exp|log|expf|logf|__expf|__logf)\s*\(") + TREE_COPIES:
+                 r"\bint\s+check_workspace\b", r"\bdouble\s+(exp_rule|log_rule|e_of)\b", r"\b(exp|log|expf|logf|__expf|__logf)\s*\(") + TREE_COPIES + VALUE_COPIES:
         assert not re.search(copy, src), copy
     assert not RULE_NAMES.search(src)      # none of the rule's constants is defined here
-    assert "wave_tree<Add>(" in src and "lane_value(" in src and "run_tree(" in src and "fold_level<Partials>(" in src
+    assert "wave_tree<Add>(" in src and "lane_value(" in src and "run_tree(" in value and "fold_level<Partials>(" in value
+    assert "check_batch(" in src and "check_targets(" in src and "sum_columns(" in src and "static_assert(MXV_QR_STATS == kV" in src
     for word in ("atomic", "asm", "__shfl", "#if MXV_"):
         assert word not in src, word
     tree_header()
@@ -94,11 +96,11 @@ def test_the_source_shares_the_rule_the_tree_and_the_host_checks():
 def test_the_launch_constants_the_module_exports_are_the_kernels():
     from gym_amd import c51, qr
 
-    src = open(SRC).read()
+    src, value = open(SRC).read(), open(VALUE).read()
     rule = open(os.path.join(CSRC, "mxv_policy_rule.hpp")).read()
     tree = open(TREE).read()
     assert f"constexpr int kLeafRows = {qr.LEAF_ROWS};" in tree and f"constexpr int kTreeFan = {qr.LEAF_ROWS};" in tree
     assert c51.LEAF_ROWS == qr.LEAF_ROWS and (c51.TILE_ROWS, c51.GRID_X, c51.MAX_BLOCKS) == (qr.TILE_ROWS, qr.GRID_X, qr.MAX_BLOCKS)
-    assert f"constexpr int kGridX = 1 << {qr.GRID_X.bit_length() - 1};" in src and qr.GRID_X & (qr.GRID_X - 1) == 0
-    assert "constexpr int kWaves = kThreads / 64;" in src and f"constexpr int kThreads = {64 * qr.TILE_ROWS};" in rule
+    assert f"constexpr int kGridX = 1 << {qr.GRID_X.bit_length() - 1};" in value and qr.GRID_X & (qr.GRID_X - 1) == 0
+    assert "constexpr int kWaves = kThreads / 64;" in value and f"constexpr int kThreads = {64 * qr.TILE_ROWS};" in rule
     assert f"constexpr int kMaxBlocks = {qr.MAX_BLOCKS};" in rule and f"constexpr int kMaxQuantiles = {qr.MAX_QUANTILES};" in src
