@@ -1,7 +1,8 @@
 // mxv_policy_host.hpp — the host side that the handle-free policy calls share (include/mxv_policy.h, include/mxv_policy_eval.h): their
 // error slots, the argument checks that run before the device is touched, and the launch.  mxv_policy.hip, mxv_gaussian.hip and
 // mxv_policy_eval.hip keep only what is their own: the ranges of their arguments, filling the kernel's struct and choosing the
-// instantiation.  mxv_ppo.hip (include/mxv_ppo.h) and mxv_vtrace.hip (include/mxv_vtrace.h) use the same Call with their own slots.
+// instantiation.  mxv_ppo.hip (include/mxv_ppo.h), mxv_vtrace.hip (include/mxv_vtrace.h) and mxv_gae.hip (include/mxv_gae.h) use the
+// same Call with their own slots.
 // Host code only: no kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +27,9 @@ struct PpoCall {   // include/mxv_ppo.h: mxv_ppo_last_error
     std::string error;
 };
 struct VtraceCall {   // include/mxv_vtrace.h: mxv_vtrace_last_error
+    std::string error;
+};
+struct GaeCall {   // include/mxv_gae.h: mxv_gae_last_error, of mxv_gae and mxv_discounted_returns
     std::string error;
 };
 struct DqnCall {   // include/mxv_dqn.h: mxv_dqn_last_error

@@ -21,7 +21,7 @@ from . import _native
 from ._policy_args import LEAF_ROWS       # rows per leaf of the sum tree, and leaves per group of a level
 from ._policy_args import _one_device, _ptr, _vector
 from ._value_loss import Bound, _outputs
-from .returns import _scalar
+from ._trajectory_args import _scalar
 
 PPO_EXPORTS = ("mxv_ppo_workspace_bytes", "mxv_ppo_advantage_moments", "mxv_ppo_clip_loss", "mxv_ppo_clip_loss_backward", "mxv_ppo_last_error")
 # indices into stats (MXV_PPO_* of the header)

@@ -12,13 +12,12 @@ gym_amd._native, and are not part of _native.EXPORTS.  Importing this module doe
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 from . import _native
+# the two constants are public names of this module; dqn.py, c51.py, qr.py and tests/test_gae_host.py take _scalar from here
+from ._trajectory_args import RING_DEPTH, VECTOR_MIN_ENVS, _bind, _prepare, _ptr, _scalar  # noqa: F401
 
 GAE_EXPORTS = ("mxv_gae", "mxv_discounted_returns", "mxv_gae_last_error", "mxv_gae_last_launch")
-RING_DEPTH = 4      # rows the kernel keeps in flight ahead of the one it consumes (kRing, gym_amd/csrc/mxv_gae.hip)
-VECTOR_MIN_ENVS = 1 << 21   # from here on (and with 16-byte alignment throughout) a lane owns four envs (kVecMinN)
 
 lib = _native.lib
 lib.mxv_gae.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -27,26 +26,7 @@ lib.mxv_gae.restype = C.c_int
 lib.mxv_discounted_returns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64]
 lib.mxv_discounted_returns.restype = C.c_int
-lib.mxv_gae_last_error.argtypes = []
-lib.mxv_gae_last_error.restype = C.c_char_p
-lib.mxv_gae_last_launch.argtypes = [C.c_void_p, C.c_void_p]
-lib.mxv_gae_last_launch.restype = C.c_int
-
-
-def _check(rc: int):
-    if rc == _native.OK:
-        return
-    msg = lib.mxv_gae_last_error().decode()
-    if rc == _native.ERR_INVALID_ARG:
-        raise ValueError(msg)
-    raise _native.MxvError(rc, msg)
-
-
-def last_launch():
-    """(envs per lane, workgroups) of this thread's last launch by gae() / discounted_returns(): 4 envs per lane is the 16-byte path."""
-    v, g = C.c_int32(), C.c_uint32()
-    _check(lib.mxv_gae_last_launch(C.byref(v), C.byref(g)))
-    return v.value, g.value
+_check, last_launch = _bind(lib, "gae", "gae() / discounted_returns()")
 
 
 def pre_step_observations(first_obs, traj_obs):
@@ -60,105 +40,6 @@ def pre_step_observations(first_obs, traj_obs):
     if tuple(first_obs.shape) != tuple(traj_obs.shape[1:]):
         raise ValueError(f"first_obs must have the shape of one row of the trajectory's obs {tuple(traj_obs.shape[1:])}, got {tuple(first_obs.shape)}")
     return t.cat((first_obs.to(traj_obs.dtype).unsqueeze(0), traj_obs[:-1]))
-
-
-def _scalar(name, v):
-    """A finite real number as a Python float: int, float, NumPy scalars, 0-dim arrays and tensors; not bool, not text."""
-    try:
-        f = None if isinstance(v, (bool, str, bytes)) else float(v)
-    except (TypeError, ValueError):
-        f = None
-    if f is None or not math.isfinite(f):
-        raise ValueError(f"{name} must be a finite number, got {v!r}")
-    return f
-
-
-def _dtype_name(t, dtypes):
-    return " or ".join(str(d) for d in dtypes)
-
-
-def _matrix(t, x, name, dtypes, shape=None):
-    """A [K, N] tensor of one of `dtypes` whose last dimension is contiguous; torch.bool is taken as a uint8 view."""
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype == t.bool and t.uint8 in dtypes:
-        x = x.view(t.uint8)
-    if x.dtype not in dtypes:
-        raise ValueError(f"{name} must be {_dtype_name(t, dtypes)}, got {x.dtype}")
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"{name} must have shape [K, N] with K, N >= 1, got {tuple(x.shape)}")
-    if shape is not None and tuple(x.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)} like reward, got {tuple(x.shape)}")
-    if x.shape[1] > 1 and x.stride(1) != 1:
-        raise ValueError(f"{name} must be contiguous in its last dimension (stride {x.stride(1)}): rows may be strided views, elements not")
-    if x.shape[0] > 1 and x.stride(0) < x.shape[1]:
-        raise ValueError(f"{name} has row stride {x.stride(0)} < N = {x.shape[1]}: rows overlap")
-    return x
-
-
-def _vector(t, x, name, n):
-    if x is None:
-        return None
-    if not isinstance(x, t.Tensor):
-        raise ValueError(f"{name} must be a torch tensor or None, got {type(x).__name__}")
-    if x.dtype != t.float32:
-        raise ValueError(f"{name} must be torch.float32, got {x.dtype}")
-    if tuple(x.shape) != (n,):
-        raise ValueError(f"{name} must have shape ({n},), got {tuple(x.shape)}")
-    if n > 1 and x.stride(0) != 1:
-        raise ValueError(f"{name} must be contiguous (stride {x.stride(0)})")
-    return x
-
-
-def _row_stride(tensors, what):
-    """The one row stride (in elements) of [K, N] tensors, which the C ABI takes once for all of them."""
-    K, N = tensors[0][1].shape
-    if K == 1:
-        return N        # a single row has no stride to agree on
-    lds = {name: x.stride(0) for name, x in tensors}
-    if len(set(lds.values())) != 1:
-        raise ValueError(f"the {what} must share one row stride (the C ABI takes a single one), got " +
-                         ", ".join(f"{k}: {v}" for k, v in lds.items()))
-    return next(iter(lds.values()))
-
-
-def _prepare(with_values, reward, terminated, truncated, values, last_value, final_values, out, out_names):
-    """Every check that needs no device — types, dtypes, shapes, strides — then the device of every tensor.  with_values: GAE (else
-    returns-to-go, which takes no `values`)."""
-    import torch as t
-
-    reward = _matrix(t, reward, "reward", (t.float32, t.float64))
-    shape = reward.shape
-    ins = [("reward", reward), ("terminated", _matrix(t, terminated, "terminated", (t.uint8,), shape)),
-           ("truncated", _matrix(t, truncated, "truncated", (t.uint8,), shape))]
-    if with_values:
-        ins.append(("values", _matrix(t, values, "values", (t.float32,), shape)))
-    if final_values is not None:
-        ins.append(("final_values", _matrix(t, final_values, "final_values", (t.float32,), shape)))
-    last_value = _vector(t, last_value, "last_value", shape[1])
-    ld = _row_stride(ins, "inputs")
-    outs = None
-    if out is not None:
-        given = (out,) if len(out_names) == 1 and isinstance(out, t.Tensor) else tuple(out)
-        if len(given) != len(out_names):
-            raise ValueError(f"out must hold {len(out_names)} tensor(s) ({', '.join(out_names)}), got {len(given)}")
-        outs = [(f"out ({name})", _matrix(t, x, f"out ({name})", (t.float32,), shape)) for name, x in zip(out_names, given)]
-    dev = reward.device
-    for name, x in ins + [("last_value", last_value)] + (outs or []):
-        if x is None:
-            continue
-        if not x.is_cuda:
-            raise ValueError(f"{name} must be a device tensor, got one on {x.device} (gym_amd has no CPU fallback)")
-        if x.device != dev:
-            raise ValueError(f"{name} is on {x.device}, reward on {dev}: all tensors must be on one device")
-    if outs is None:
-        outs = [(name, t.empty(tuple(shape), dtype=t.float32, device=dev)) for name in out_names]
-    ld_out = _row_stride(outs, "outputs")
-    return t, dict(ins), last_value, [x for _, x in outs], ld, ld_out
-
-
-def _ptr(x):
-    return None if x is None else x.data_ptr()
 
 
 def gae(reward, terminated, truncated, values, last_value=None, *, gamma: float = 0.99, lam: float = 0.95, final_values=None, out=None):
@@ -175,7 +56,8 @@ def gae(reward, terminated, truncated, values, last_value=None, *, gamma: float 
     rounding per operation, bit-equal to tests/gae_host.py; the episode cut is a select, so a NaN of a later episode never crosses a
     boundary.  gamma, lam: finite real numbers.  Runs on the current stream, no synchronisation."""
     gamma, lam = _scalar("gamma", gamma), _scalar("lam", lam)
-    t, ins, lv, outs, ld, ld_out = _prepare(True, reward, terminated, truncated, values, last_value, final_values, out, ("advantages", "returns"))
+    t, ins, lv, outs, ld, ld_out = _prepare([("reward", reward), ("terminated", terminated), ("truncated", truncated), ("values", values)],
+                                            last_value, final_values, out, ("advantages", "returns"), bare_out=False)
     r = ins["reward"]
     K, N = r.shape
     with t.cuda.device(r.device):
@@ -190,7 +72,8 @@ def discounted_returns(reward, terminated, truncated, *, gamma: float = 0.99, la
     terminated | truncated is set (bootstrapping with final_values where only truncated is), G_K = last_value (None = 0).  Arguments,
     layout and arithmetic as gae(); `out` is one float32 [K, N] tensor."""
     gamma = _scalar("gamma", gamma)
-    t, ins, lv, outs, ld, ld_out = _prepare(False, reward, terminated, truncated, None, last_value, final_values, out, ("returns",))
+    t, ins, lv, outs, ld, ld_out = _prepare([("reward", reward), ("terminated", terminated), ("truncated", truncated)], last_value,
+                                            final_values, out, ("returns",), bare_out=True)
     r = ins["reward"]
     K, N = r.shape
     with t.cuda.device(r.device):

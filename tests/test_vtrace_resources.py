@@ -6,7 +6,8 @@ memory); the occupancy and the vector registers are at least / at most what the 
 (DESIGN.md §16 records the figures).  And the ring stays deep: in the K loop of the
 instantiations without final_values — one basic block per group of steps — every wait in front of a row's arithmetic is a counted one
 that leaves the loads of kRing later rows in flight (6 loads per row, one more for float64 rewards at V = 4), never vmcnt(0).  The
-source is in both build scripts, includes the shared rule and defines no copy of it, and uses no atomics, LDS or assembly."""
+source is in both build scripts, includes the shared rule and defines no copy of it, and uses no atomics, LDS or assembly; it and
+mxv_gae.hip take the walk, the host checks and the limits from mxv_trajectory.hpp and the rule header and define no copy of those."""
 import os
 import re
 import shutil
@@ -87,6 +88,19 @@ def test_the_source_is_built_by_both_scripts_and_shares_the_rule():
         assert not re.search(copy, code), copy
     for word in ("atomic", "asm", "__shfl", "__shared__", "__syncthreads"):
         assert word not in code, word
+    # mxv_gae.hip takes the launch shape and the limits from the same header, and both take what the two recurrences share from
+    # mxv_trajectory.hpp: neither defines a copy
+    gae = re.sub(r"//.*", "", policy_host.rule_block("mxv_gae.hip")[1])
+    assert "kThreads" in gae
+    for copy in (r"\bkThreads\s*=", r"\bkMaxBlocks\s*=", r"\bkMaxElems\s*="):
+        assert not re.search(copy, gae), copy
+    shared = re.sub(r"//.*", "", open(os.path.join(ROOT, "gym_amd", "csrc", "mxv_trajectory.hpp")).read())
+    for name, text in (("mxv_gae.hip", gae), ("mxv_vtrace.hip", code)):
+        assert '#include "mxv_trajectory.hpp"' in text and "MXV_TRAJECTORY_WALK(" in text, name
+        for copy in (r"\bshares_bytes\s*\(\s*Span\b", r"\bstruct\s+Span\b", r"\bto_f32\s*\(\s*double\b", r"\bkRing\s*=", r"\bkVecMinN\s*=",
+                     r"sched_barrier", r"\bstruct\s+LastLaunch\b"):
+            assert not re.search(copy, text), (name, copy)
+            assert re.search(copy, shared), copy
     for script in ("build.sh", "build_asan.sh"):
         assert "mxv_vtrace.hip" in open(os.path.join(ROOT, "gym_amd", "csrc", script)).read(), script
     flags = open(os.path.join(ROOT, "gym_amd", "csrc", "build.sh")).read()
