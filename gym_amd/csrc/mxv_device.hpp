@@ -891,11 +891,39 @@ struct Env<MXV_MOUNTAINCAR_CONT> {
             const double g = 0.0025 * mx_cos<SAFE, fma3_for<MXV_MOUNTAINCAR_CONT>()>((double)three_p);
             const float inc = clipped ? (float)(force_py * power - g) : (fp - (float)g);
             velocity = velocity + inc;
-            velocity = clamp_range_hi_first(velocity, (float)(-max_speed), (float)max_speed);
-            position = position + velocity;
-            position = clamp_range_hi_first(position, (float)min_position, (float)max_position);
-            if (position == (float)min_position && velocity < 0) velocity = 0;
-            term = position >= (float)goal_position && velocity >= (float)goal_velocity;
+            if constexpr (DEF == PM_DEFAULT) {   // (the default attributes: float32 and float64 comparisons agree, see below)
+                velocity = clamp_range_hi_first(velocity, (float)(-max_speed), (float)max_speed);
+                position = position + velocity;
+                position = clamp_range_hi_first(position, (float)min_position, (float)max_position);
+                if (position == (float)min_position && velocity < 0) velocity = 0;
+                term = position >= (float)goal_position && velocity >= (float)goal_velocity;
+            } else {
+                // A clamp that acts assigns the attribute itself, a Python float (:150, :152, :155, :157), and :159 the int 0: from there
+                // on that variable compares in float64 with the attributes, while an np.float32 compares in float32 (NEP 50).  v_py /
+                // p_py: the variable is such a Python number, vd / pd its value.  It shows only with changed attributes: a goal_velocity
+                // within float32 rounding of max_speed, a max_position within float32 rounding of goal_position, 0 against a goal_velocity
+                // that float32 flushes to zero.
+                const float msf = (float)max_speed, nmsf = (float)(-max_speed);
+                const bool v_hi = velocity > msf;
+                const bool v_lo = v_hi ? (max_speed < -max_speed) : (velocity < nmsf);
+                bool v_py = v_hi || v_lo;
+                double vd = v_lo ? -max_speed : max_speed;
+                velocity = clamp_range_hi_first(velocity, nmsf, msf);
+                position = position + velocity;
+                const float minpf = (float)min_position, maxpf = (float)max_position;
+                const bool p_hi = position > maxpf;
+                const bool p_lo = p_hi ? (max_position < min_position) : (position < minpf);
+                const bool p_py = p_hi || p_lo;
+                const double pd = p_lo ? min_position : max_position;
+                position = clamp_range_hi_first(position, minpf, maxpf);
+                if ((p_py ? (pd == min_position) : (position == minpf)) && (v_py ? (vd < 0) : (velocity < 0))) {
+                    velocity = 0;
+                    vd = 0;
+                    v_py = true;
+                }
+                term = (p_py ? (pd >= goal_position) : (position >= (float)goal_position)) &&
+                       (v_py ? (vd >= goal_velocity) : (velocity >= (float)goal_velocity));
+            }
             s[0] = (double)position;
             s[1] = (double)velocity;
         }

@@ -350,14 +350,24 @@ static void mcc_step(const double *P, double *s, int fresh, float a0, float *obs
             inc = (float)(force_py * power - g);       /* python float, cast when added to f32 */
         }
         velocity = velocity + inc;
-        if (velocity > (float)max_speed) velocity = (float)max_speed;
-        if (velocity < (float)(-max_speed)) velocity = (float)(-max_speed);
-        position = position + velocity;
-        if (position > (float)max_position) position = (float)max_position;
-        if (position < (float)min_position) position = (float)min_position;
-        if (position == (float)min_position && velocity < 0) velocity = 0;
-        term = (position >= (float)goal_position && velocity >= (float)goal_velocity);
-        s[0] = (double)position;
+        /* A clamp that acts assigns the attribute itself — a python float — so from there on that variable compares in float64
+         * (python float against python float), while an np.float32 compares in float32 (NEP 50: the python float is cast).
+         * vpy / ppy: the variable is a python float (or the int 0 of :159) and vd / pd holds it. */
+        int vpy = 0, ppy = 0;
+        double vd = 0.0, pd = 0.0;
+        if (velocity > (float)max_speed) { vd = max_speed; vpy = 1; }                                   /* :149-150 */
+        if (vpy ? (vd < -max_speed) : (velocity < (float)(-max_speed))) { vd = -max_speed; vpy = 1; }   /* :151-152 */
+        if (vpy) velocity = (float)vd;
+        position = position + velocity;                         /* :153 np.float32 += python float -> float32 */
+        if (position > (float)max_position) { pd = max_position; ppy = 1; }                             /* :154-155 */
+        if (ppy ? (pd < min_position) : (position < (float)min_position)) { pd = min_position; ppy = 1; } /* :156-157 */
+        if (ppy) position = (float)pd;
+        if ((ppy ? (pd == min_position) : (position == (float)min_position)) && (vpy ? (vd < 0) : (velocity < 0))) { /* :158-159 */
+            vd = 0.0; vpy = 1; velocity = 0;
+        }
+        term = (ppy ? (pd >= goal_position) : (position >= (float)goal_position)) &&
+               (vpy ? (vd >= goal_velocity) : (velocity >= (float)goal_velocity));                      /* :162-164 */
+        s[0] = (double)position;                                /* :171 np.array(..., dtype=np.float32) */
         s[1] = (double)velocity;
     }
     double reward_ = term ? 100.0 : 0.0;               /* :166-168 */

@@ -123,12 +123,15 @@ def compare_step(tag, got, ref, done_ref, strict):
                                    err_msg=f"{tag}: fp64 state")
 
 
-def run_p1(engine_cls, name, strict, kind="p1", golden=None):
+def run_p1(engine_cls, name, strict, kind="p1", golden=None, params=None):
     """Single raw-env steps from hand-set states (golden <env>_p1.npz; kind="p1_threshold": Acrobot states whose post-step
-    height sits within ulps of the termination threshold, make_golden_goal.py; golden=: vectors made on the spot)."""
+    height sits within ulps of the termination threshold, make_golden_goal.py; golden=: vectors made on the spot; params=: the
+    parameter vector the reference ran with, handed to the engine's set_params)."""
     g = load_golden(name, kind) if golden is None else golden
     n = len(g["action"])
     eng = engine_cls(name, n, 0, autoreset=False)
+    if params is not None:
+        eng.set_params(params)
     elapsed = np.where(g["fresh"] == 1, 0, 5).astype(np.int32)
     eng.set_state(g["state0"].T, elapsed)
     obs, rew, term, trunc, fin = eng.step(g["action"])
@@ -139,6 +142,58 @@ def run_p1(engine_cls, name, strict, kind="p1", golden=None):
                truncated=np.zeros(n, dtype=bool), final_obs=g["obs"], state=g["state1"], elapsed=elapsed + 1)
     compare_step(f"{name} {kind.upper()}", got, ref, done, strict)
     return int(term.sum())
+
+
+EDGE_ENVS = ["CartPole", "Pendulum", "MountainCar", "MountainCarContinuous"]
+
+
+def edge_groups(name):
+    """<env>_p1_edges.npz (tests/golden/make_golden_edges.py: exactly-determined states on, one ulp inside and one ulp outside every
+    comparison) split by the parameter vector the reference ran with: [(params or None for the defaults, {array name: rows})]."""
+    from oracle import oracle
+
+    g = load_golden(name, "p1_edges")
+    default = oracle.default_params(ENV_IDS[name])
+    out = []
+    for pv in np.unique(g["params"], axis=0):
+        rows = np.flatnonzero((g["params"] == pv).all(axis=1))
+        out.append((None if np.array_equal(pv, default) else pv, {k: g[k][rows] for k in g.files}))
+    out.sort(key=lambda t: t[0] is not None)          # the default rows first
+    assert out[0][0] is None
+    return out
+
+
+def check_edge_classes(name):
+    """The class counts tests/golden/make_golden_edges.py asserted before it wrote <env>_p1_edges.npz, re-asserted from `klass`."""
+    klass = [str(k) for k in load_golden(name, "p1_edges")["klass"]]
+
+    def count(pred):
+        return sum(1 for k in klass if pred(k))
+
+    assert len(klass) <= 4096
+    if name == "CartPole":        # per parameter set and bound: >= 64 moving rows on / one ulp inside / one ulp outside, >= 64 FMA-splitting rows
+        for s in ("default", "moved"):
+            for b in ("x+", "x-", "th+", "th-"):
+                for pos in ("on", "in", "out"):
+                    assert count(lambda k: k in (f"{s}|{b}:{pos}", f"{s}|{b}:{pos}:split")) >= 64, (s, b, pos)
+                    assert count(lambda k: k == f"{s}|{b}:{pos}:v0") >= 4, (s, b, pos)
+                assert count(lambda k: k.startswith(f"{s}|{b}:") and k.endswith(":split")) >= 64, (s, b)
+    elif name in ("MountainCar", "MountainCarContinuous"):
+        want = ["goal:on", "goal:below", "goal:above", "max:on", "max:clamped", "min:on", "min:above", "min:clamped", "gv:eq", "gv:above"]
+        if name == "MountainCarContinuous":
+            want += ["gv:above32", "zero:gv", "clamp:goal", "term:reward", "act:max", "act:max+1", "act:max+far", "act:min", "act:min-1", "act:min-far"]
+            want = [p + k for p in ("f64|", "f32|") for k in want]
+        for w in want:
+            assert count(lambda k: k == w) >= 32, (name, w)
+    else:
+        assert count(lambda k: k == "speed+") >= 32 and count(lambda k: k == "speed-") >= 32
+        for t in ("max", "max+1", "max+far", "min", "min-1", "min-far", "+0", "-0"):
+            assert count(lambda k: k == f"torque:{t}:th0") >= 32 and count(lambda k: k == f"torque:{t}") >= 32, t
+        for kk in range(-9, 10):
+            for tag in ("at", "lo", "hi", "far"):
+                assert count(lambda k: k == f"kpi:{kk}:{tag}") >= 1, (kk, tag)
+        assert count(lambda k: k == "mag") >= 26 and count(lambda k: k == "mag:free") >= 64
+    return len(klass)
 
 
 def run_p1_variants(engine_cls, name, strict):
