@@ -49,6 +49,9 @@ _LAZY = {
     "NStepPrioritizedReplayBuffer": ("gym_amd.nstep", "NStepPrioritizedReplayBuffer"),
     "quantile_dqn_loss": ("gym_amd.qr", "quantile_dqn_loss"),
     "quantile_q_values": ("gym_amd.qr", "quantile_q_values"),
+    "dqn_targets": ("gym_amd.targets", "dqn_targets"),
+    "categorical_targets": ("gym_amd.targets", "categorical_targets"),
+    "quantile_targets": ("gym_amd.targets", "quantile_targets"),
 }
 
 def __getattr__(name):

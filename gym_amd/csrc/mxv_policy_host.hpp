@@ -50,6 +50,9 @@ struct NStepCall {   // include/mxv_nstep.h: mxv_nstep_last_error
 struct QrCall {   // include/mxv_qr.h: mxv_qr_last_error
     std::string error;
 };
+struct TargetsCall {   // include/mxv_targets.h: mxv_targets_last_error
+    std::string error;
+};
 
 namespace policy_host {
 
