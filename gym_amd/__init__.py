@@ -52,6 +52,9 @@ _LAZY = {
     "dqn_targets": ("gym_amd.targets", "dqn_targets"),
     "categorical_targets": ("gym_amd.targets", "categorical_targets"),
     "quantile_targets": ("gym_amd.targets", "quantile_targets"),
+    "soft_q_targets": ("gym_amd.sac", "soft_q_targets"),
+    "twin_q_loss": ("gym_amd.sac", "twin_q_loss"),
+    "soft_policy_loss": ("gym_amd.sac", "soft_policy_loss"),
 }
 
 def __getattr__(name):

@@ -12,7 +12,7 @@ mkdir -p "$out"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 SAN=(-fsanitize=address,undefined -fno-sanitize=alignment,vptr,function -fno-gpu-sanitize -fno-omit-frame-pointer -g)
 FLAGS=(--offload-arch=gfx950 -O1 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-result "${SAN[@]}")
-srcs=(mxv_kernels.hip mxv_api.cpp mxv_norm.hip mxv_subnorm.hip mxv_tab.hip mxv_bj.hip mxv_placed.hip mxv_render.hip mxv_gae.hip mxv_policy.hip mxv_gaussian.hip mxv_policy_eval.hip mxv_ppo.hip mxv_vtrace.hip mxv_dqn.hip mxv_replay.hip mxv_prio.hip mxv_c51.hip mxv_squashed.hip mxv_nstep.hip mxv_qr.hip mxv_targets.hip)
+srcs=(mxv_kernels.hip mxv_api.cpp mxv_norm.hip mxv_subnorm.hip mxv_tab.hip mxv_bj.hip mxv_placed.hip mxv_render.hip mxv_gae.hip mxv_policy.hip mxv_gaussian.hip mxv_policy_eval.hip mxv_ppo.hip mxv_vtrace.hip mxv_dqn.hip mxv_replay.hip mxv_prio.hip mxv_c51.hip mxv_squashed.hip mxv_nstep.hip mxv_qr.hip mxv_targets.hip mxv_sac.hip)
 objs=(); pids=()
 for s in "${srcs[@]}"; do
     o="$out/${s%.*}.o"; rm -f "$o"; objs+=("$o")

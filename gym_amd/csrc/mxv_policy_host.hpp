@@ -53,6 +53,9 @@ struct QrCall {   // include/mxv_qr.h: mxv_qr_last_error
 struct TargetsCall {   // include/mxv_targets.h: mxv_targets_last_error
     std::string error;
 };
+struct SacCall {   // include/mxv_sac.h: mxv_sac_last_error
+    std::string error;
+};
 
 namespace policy_host {
 
